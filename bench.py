@@ -220,6 +220,38 @@ def output_digest(hard, n_soft, best_phase):
     return h.hexdigest()
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, hard, soft, n_soft, best_phase, min_margin, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives for one step -- per carrier the hard symbols, the soft
+    symbols, the timing phase picked and the smallest decision margin (BatchDemodulator.process) -- as float .npy files
+    under `path`, so that the outputs of two builds can be compared array for array.  hard.npy [rows][max_soft] float32
+    holds -1 past a carrier's n_soft - 1 symbols, soft.npy [rows][max_soft][2] (re, im) 0 past its n_soft: the buffers'
+    tails are no output.  When the batch is larger than `limit` bytes, a fixed seeded sample of the carriers is written,
+    in ascending order; rows.npy names them.  Returns what the result line says about it."""
+    n_rows, ms = hard.shape
+    real = np.float32 if soft.dtype == np.complex64 else np.float64
+    per_row = ms * 4 + ms * 2 * np.dtype(real).itemsize + 4 * 8   # hard, soft, n_soft / best_phase / min_margin / rows
+    keep = min(n_rows, max(1, int(limit // per_row)))
+    rows = np.arange(n_rows) if keep == n_rows else np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+    ns = n_soft[rows].astype(np.int64)
+    col = np.arange(ms)[None, :]
+    arrays = {
+        "hard": np.where(col < np.maximum(ns - 1, 0)[:, None], hard[rows].astype(np.float32), np.float32(-1)),
+        "soft": np.where((col < ns[:, None])[:, :, None], np.ascontiguousarray(soft[rows]).view(real).reshape(keep, ms, 2), 0).astype(real),
+        "n_soft": ns.astype(np.float64),
+        "best_phase": best_phase[rows].astype(np.float64),
+        "min_margin": min_margin[rows].astype(np.float64),
+        "rows": rows.astype(np.float64),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": os.path.abspath(path), "files": [n + ".npy" for n in arrays], "rows": keep, "of_rows": n_rows,
+            "bytes": int(sum(a.nbytes for a in arrays.values())), "step": "the last timed step"}
+
+
 def digest_key(carriers, chunk, fmt, rate, rank, shared):
     return f"{fmt}:{carriers}x{chunk}@{rate:g}:rank{rank}" + (":shared" if shared else "")
 
@@ -425,7 +457,14 @@ def main():
                          "auto = 3 (up to three steps in flight); 1 = one plan, steps strictly one after the other")
     ap.add_argument("--pmc-child", action="store_true",
                     help="(internal) the short run rocprofv3 counts HBM traffic on: noise input, no output check, no side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB: a fixed seeded sample of the carriers beyond that; rank 0's carriers); see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "reference":
+        ap.error("--dump-outputs: the headline workload (--mode reference) only")
     # which workload: see --total-carriers.  (N = 1: the two coincide -- 1024 carriers on the one GPU.)
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     args.weak_side = False
@@ -563,6 +602,8 @@ def main():
     ev_ms = bd.time_end()
     barrier()
     dt = time.perf_counter() - t0
+    # --dump-outputs: the last timed step's outputs, downloaded before anything else runs on the plans
+    dumped = dump_outputs(args.dump_outputs, *bd.download()) if (args.dump_outputs and rank == 0) else None
     # the per-kernel pass: the same `steps` passes again with a HIP-event pair around every launch (the roofline's kernel
     # time).  The events themselves cost ~5 us per launch, which is why this is not the region `value` is taken from.
     bd.time_begin(per_stage=True)
@@ -723,6 +764,8 @@ def main():
             },
             "hbm_ceiling_measured": ceil or None,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1 and not args.pmc_child:   # reported on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.chunk)
             try:

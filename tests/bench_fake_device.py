@@ -15,26 +15,32 @@ class _Info:
 
 
 class FakeBatchDemodulator:
+    enqueued = 0   # steps enqueued so far on every plan of the process: a plan's soft outputs carry the number of its last
+
     def __init__(self, rate, chunk, carriers, fmt, device=0, **kw):
         self.carriers, self.info = carriers, _Info()
         self.rank = int(os.environ.get("RANK", "0"))
         self.fmt, self.soft_dtype = 0, np.complex128
+        self.last_step = 0
 
     def sync(self): pass
     def wait_for(self, other): pass
     def alloc_device_io(self, shared_input=False): pass
     def upload(self, iq, freq_offsets=None, pre_shifts=None): pass
-    def enqueue(self): pass
     def time_begin(self, per_stage=True): pass
     def time_end(self): return 1.0 + self.rank
     def stage_times(self): return {"dec_block": 0.5, "dec_carry": 0.01, "lpf_block": 0.3, "finish": 0.03}
     def close(self): pass
 
+    def enqueue(self):
+        FakeBatchDemodulator.enqueued += 1
+        self.last_step = FakeBatchDemodulator.enqueued
+
     def download(self):
         rows, ms = self.carriers, self.info.max_soft
         hard = np.full((rows, ms), self.rank, dtype=np.uint8)
         n_soft = np.full(rows, 30 + self.rank, dtype=np.int32)
-        return hard, np.zeros((rows, ms), np.complex128), n_soft, np.zeros(rows, np.int32), np.zeros(rows)
+        return hard, np.full((rows, ms), self.last_step + 1j * self.rank), n_soft, np.zeros(rows, np.int32), np.zeros(rows)
 
 
 class _HostMem:
