@@ -189,7 +189,8 @@ TDM_API int tdm_plan_resize(tdm_plan *plan, int64_t n_samples);
  *  min_margin    [n_carriers] min |phase - threshold| over the decisions (rad), may be NULL
  * tdm_process:        all pointers are HOST memory; blocking.
  * tdm_process_device: all pointers are DEVICE memory (pre_shift/freq_offset too); enqueues on
- *                     `stream` (a hipStream_t, NULL = default) and returns; tdm_plan_sync waits. */
+ *                     `stream` (a hipStream_t, NULL = the plan's own stream) and returns; tdm_plan_sync
+ *                     waits. */
 TDM_API int tdm_process(tdm_plan *plan, const void *iq, int64_t carrier_stride_samples,
                 const double *pre_shift_hz, const double *freq_offset_hz, uint8_t *hard, double *soft,
                 int32_t *n_soft, int32_t *best_phase, double *min_margin);
@@ -215,14 +216,18 @@ TDM_API int tdm_set_stream(void *stream);
 TDM_API int tdm_plan_stream(tdm_plan *plan, void **stream);
 /* Device-side ordering between two plans of one device (no host synchronisation): what is enqueued on `plan`'s stream from
  * now on starts after everything enqueued so far on `other`'s stream has finished.  Plans are independent objects on their
- * own streams and normally overlap (a large batch run as two plans of half the carriers each is faster than as one, see
- * tetraear_amd/batch.py SplitBatchDemodulator); this call is for the places where they must not -- a consumer plan behind a
+ * own streams and normally overlap (steps of one batch geometry handed to two or three plans in turn run faster than on one,
+ * see tetraear_amd/batch.py PipelinedBatchDemodulator); this call is for the places where they must not -- a consumer plan behind a
  * producer plan, or timing one plan's launches alone on the device.  No counterpart in the reference. */
 TDM_API int tdm_plan_wait_for(tdm_plan *plan, tdm_plan *other);
 /* Host-fed streaming: n_batches consecutive batches, each laid out like one
  * tdm_process call (n_carriers x n_samples back to back; outputs [n_batches][n_carriers][max_soft]...).
  * The host->device copy of batch i+1 and the device->host copy of batch i-1 overlap the kernels of
- * batch i (two device slots, three streams; the caller's buffers are pinned in place for the call).
+ * batch i (two device slots, three streams).  The input and the hard / soft outputs are page-locked in place for the
+ * call (hipHostRegister) and released before it returns; a buffer that is page-locked already (tdm_host_register,
+ * hipHostMalloc) is used as it is and stays registered -- the caller's tdm_host_unregister still owns it.  Results do not
+ * depend on the pinning, only how far the copies overlap.  n_soft / best_phase / min_margin are copied unpinned; best_phase,
+ * min_margin and freq_offset_hz may be NULL.  Plans with rows_per_chunk > 1 are refused (TDM_ERR_UNSUPPORTED).
  * freq_offset_hz is per carrier and applies to every batch.  Consecutive 256 Ki-sample chunks of one
  * recording are independent (the reference is stateless per read, processor.py:221-273), so a long
  * capture is simply fed as rows of successive batches.                                              */

@@ -401,9 +401,10 @@ def test_config5_10Msps_q41_all_400_grid_carriers():
     small.close()
 
 
-def test_recorded_file_ingest_pipelined(tmp_path):
-    """BASELINE config 1 shape: a cu8 'recording' cut into 262144-sample reads; every read must equal
-    the oracle's process() of that read (chunks are stateless), through the copy/compute pipeline."""
+def test_recorded_file_ingest_every_read(tmp_path):
+    """BASELINE config 1 shape: a cu8 'recording' FILE cut into 65536-sample reads by demodulate_recording (iter_recording:
+    two page-locked buffers filled in turn by a reader thread, one plan, 4 reads per call); every read -- 11 whole ones and
+    the shorter last one -- must equal the oracle's process() of that read (chunks are stateless)."""
     from oracle.oracle import OracleSignalProcessor
     from tetraear_amd import synth
     from tetraear_amd.ingest import demodulate_recording
@@ -413,11 +414,11 @@ def test_recorded_file_ingest_pipelined(tmp_path):
     u8.tofile(path)
     outs = demodulate_recording(str(path), 2.4e6, chunk=chunk, freq_offset=1171.875, rows_per_batch=4)
     assert len(outs) == n_chunks + 1
-    for i in (0, 3, 4, 7, 8, 10, 11):
+    for i in range(n_chunks + 1):
         lo = 2 * chunk * i
         hi = lo + 2 * (chunk if i < n_chunks else tail)
         ref = OracleSignalProcessor(2.4e6).process(synth.cu8_to_c128(u8[lo:hi]), 1171.875)
-        np.testing.assert_array_equal(outs[i], ref)
+        np.testing.assert_array_equal(outs[i], ref, err_msg=f"read {i}")
 
 
 @pytest.mark.gpu

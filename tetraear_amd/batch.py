@@ -300,12 +300,26 @@ class PipelinedBatchDemodulator:
     samples (tools/split_bench.py, round 6) one plan 0.163 / 0.459 / 0.836 ms per step, two plans in turn 0.123 / 0.397 /
     0.788, three 0.109 / 0.395 / 0.781; the same batch cut into two HALVES on two streams 0.152 / 0.425 / 0.802 (smaller
     launches lose more than the overlap wins), "whole dispatch rounds on the raw-byte kernel + the rest on the double-based
-    one" slower than one plan.  A capture loop gets the same by giving chunk k to plan k % depth -- `upload(..., slot=k)`
-    then `enqueue()`; each plan's outputs are those of a lone plan bit for bit (every plan's digest is checked by the
-    bench).
+    one" slower than one plan.  Each plan's outputs are those of a lone plan bit for bit (every plan's digest is checked by
+    the bench).
 
-    The methods are BatchDemodulator's device-resident ones.  `upload` without a slot fills every plan's input (the bench:
-    one resident batch); `download` returns the outputs of the step enqueued last, `download_all` every plan's.
+    A capture loop gives chunk k to slot k (plan k % depth) and collects it one round later, when that plan is about to be
+    reused:
+
+        pl = PipelinedBatchDemodulator(fs, n, rows, "cu8", depth=3)
+        pl.alloc_device_io()
+        for k, chunk in enumerate(chunks):
+            if k >= pl.depth:
+                outs[k - pl.depth] = pl.download(slot=k)    # chunk k - depth: it ran on the plan slot k is about to reuse
+            pl.upload(chunk, freq_offsets=f, slot=k)        # waits for that plan's step in flight, and for no other plan
+            pl.enqueue(slot=k)
+        for k in range(max(len(chunks) - pl.depth, 0), len(chunks)):
+            outs[k] = pl.download(slot=k)
+
+    `upload` is a blocking copy on the null stream, which the plans' non-blocking streams do not order: it therefore waits
+    for the plan it writes (with a slot) or for every plan (without one: every plan's input, one resident batch for all
+    steps -- the bench).  `enqueue()` / `download()` without a slot take turns: the step goes to the next plan, `download`
+    returns the outputs of the step enqueued last; `download_all` returns every plan's.
     Per-stage timing (`time_begin(per_stage=True)`) orders the plans ONE AFTER THE OTHER on the device (tdm_plan_wait_for),
     so that every launch is timed alone; `stage_times` then average over the plans.
     """
@@ -344,26 +358,37 @@ class PipelinedBatchDemodulator:
             p.alloc_device_io(shared_input)
 
     def upload(self, iq, freq_offsets=None, pre_shifts=None, slot=None):
-        """slot None: every plan's input buffer (one resident batch for all steps); slot k: the input of step k's plan"""
+        """slot None: every plan's input buffer (one resident batch for all steps); slot k: the input of plan k % depth.
+        The copy is a blocking one on the null stream, not ordered after a step still running on the plan's own stream:
+        the plan it writes is waited for first (and only that plan)."""
         for p in (self.plans if slot is None else [self.plans[int(slot) % self.depth]]):
+            p.sync()
             p.upload(iq, freq_offsets, pre_shifts)
 
-    def enqueue(self):
-        p = self.plans[self._turn]
-        if self._serial and self.depth > 1:
+    def enqueue(self, slot=None):
+        """slot None: the step goes to the next plan in turn; slot k: to plan k % depth, and the turn moves on from there"""
+        i = self._turn if slot is None else int(slot) % self.depth
+        p = self.plans[i]
+        if self._serial and self.depth > 1 and i != self._last:
             # per-stage timing: this step starts after the previous one has finished -- on the device, no host round trip
             p.wait_for(self.plans[self._last])
         p.enqueue()
-        self._last = self._turn
-        self._turn = (self._turn + 1) % self.depth
+        self._last = i
+        self._turn = (i + 1) % self.depth
 
     def sync(self):
         for p in self.plans:
             p.sync()
 
-    def download(self):
-        self.sync()
-        return self.plans[self._last].download()
+    def download(self, slot=None):
+        """slot None: the outputs of the step enqueued last (after waiting for every plan); slot k: plan k % depth's outputs,
+        waiting for that plan only"""
+        if slot is None:
+            self.sync()
+            return self.plans[self._last].download()
+        p = self.plans[int(slot) % self.depth]
+        p.sync()
+        return p.download()
 
     def download_all(self):
         self.sync()

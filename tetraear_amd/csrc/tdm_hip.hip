@@ -73,11 +73,15 @@ static int fail(int code, const std::string &msg)
     return code;
 }
 
+// A failed call also leaves the runtime's per-thread last error set; it is cleared here, where the failure is reported,
+// so that the hipGetLastError after a LATER, unrelated launch does not report it a second time.
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
+        if (e_ != hipSuccess) {                                                                    \
+            (void)hipGetLastError();                                                               \
             return fail(TDM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
+        }                                                                                          \
     } while (0)
 
 static int use_device(int device)
@@ -1255,10 +1259,19 @@ int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, con
     const size_t in_bytes = (size_t)rows * h.n * fmt_bytes(plan->fmt);
     const size_t soft_elem = plan->mode != TDM_MODE_REFERENCE ? 2 * sizeof(float) : 2 * sizeof(double);
     const size_t hard_bytes = (size_t)rows * h.max_soft, soft_bytes = (size_t)rows * h.max_soft * soft_elem;
-    // pin the caller's buffers in place so the copies are truly asynchronous (best effort)
-    const bool pin_in = hipHostRegister((void *)iq, in_bytes * n_batches, hipHostRegisterDefault) == hipSuccess;
-    const bool pin_h = hipHostRegister(hard, hard_bytes * n_batches, hipHostRegisterDefault) == hipSuccess;
-    const bool pin_s = hipHostRegister(soft, soft_bytes * n_batches, hipHostRegisterDefault) == hipSuccess;
+    // pin the caller's buffers in place so the copies are truly asynchronous (best effort).  A buffer that is page-locked
+    // already (tdm_host_register, hipHostMalloc) is left alone: the runtime accepts a second hipHostRegister of a
+    // registered range, and the hipHostUnregister at the end would then drop the caller's own registration.
+    // (hipHostGetFlags does not see a hipHostRegister'ed range; the pointer's attributes do: type host, also inside it)
+    auto pin = [](const void *p, size_t bytes) {
+        void *q = const_cast<void *>(p);
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeHost) return false;
+        return hipHostRegister(q, bytes, hipHostRegisterDefault) == hipSuccess;
+    };
+    const bool pin_in = pin(iq, in_bytes * n_batches);
+    const bool pin_h = pin(hard, hard_bytes * n_batches);
+    const bool pin_s = pin(soft, soft_bytes * n_batches);
     (void)hipGetLastError();
     struct Slot {
         void *iq = nullptr; uint8_t *hard = nullptr; void *soft = nullptr; int32_t *ns = nullptr, *bp = nullptr; double *mm = nullptr;
@@ -1290,6 +1303,7 @@ int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, con
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) {                                                            \
+            (void)hipGetLastError();                                                       \
             rc = fail(TDM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
             cleanup();                                                                     \
             return rc;                                                                     \
