@@ -9,7 +9,8 @@
  *
  * Conventions
  *   - plain C, no exceptions cross the ABI; every call returns 0 (TDM_OK) or a negative
- *     tdm_status; tdm_last_error() gives the text for the calling thread.
+ *     tdm_status; tdm_last_error() gives the text for the calling thread.  (One exception:
+ *     tdm_stream_collect without waiting returns the positive TDM_NOT_READY.)
  *   - the caller owns every buffer it passes; a plan owns its device scratch.
  *   - a plan is not thread-safe (one caller at a time, like the reference instance,
  *     ui/modern.py:1857); the library is.
@@ -27,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TDM_VERSION 102 /* 0.1.2: + tdm_plan_wait_for (0.1.1: tdm_plan_info grew by gardner_segments) -- a binding checks tdm_version() against the header it was written for */
+#define TDM_VERSION 103 /* 0.1.3: + tdm_stream_* and tdm_link_ceiling (0.1.2: + tdm_plan_wait_for; 0.1.1: tdm_plan_info grew by gardner_segments) -- a binding checks tdm_version() against the header it was written for */
 
 #if defined(__GNUC__)
 #define TDM_API __attribute__((visibility("default")))
@@ -41,7 +42,8 @@ typedef enum tdm_status {
     TDM_ERR_NO_DEVICE = -2,  /* no usable gfx950 device / HIP runtime failure at init */
     TDM_ERR_HIP = -3,        /* a HIP call failed (text in tdm_last_error) */
     TDM_ERR_NOMEM = -4,
-    TDM_ERR_UNSUPPORTED = -5
+    TDM_ERR_UNSUPPORTED = -5,
+    TDM_NOT_READY = 1        /* tdm_stream_collect(wait = 0): the oldest step has not finished yet (not an error) */
 } tdm_status;
 
 /* IQ sample formats accepted on the wire (signal/capture.py:143-158 hands over complex128
@@ -109,7 +111,9 @@ TDM_API int tdm_last_error(char *buf, size_t buflen);
  *   "gardner_segments" what tdm_plan_option "gardner_segments" sets per plan, for TDM_MODE_TETRA_GARDNER plans created from
  *                     now on: 0 whole chunks, 1 the default, K > 1 at most K pieces, -1 fitted to the batch   (default 1)
  *   "pfb_direct"      1: channeliser plans created from now on use the direct-DFT kernel                     (default 0)
- *   "pfb_rounds"      > 0: rounds per channeliser workgroup, for plans created from now on                  (default 0: computed) */
+ *   "pfb_rounds"      > 0: rounds per channeliser workgroup, for plans created from now on                  (default 0: computed)
+ *   "stream_wc"       1: tdm_stream objects created from now on allocate their page-locked inputs write-combined
+ *                     (hipHostMallocWriteCombined: the CPU only writes them; an A/B of tools/host_fed_bench.py)   (default 0) */
 TDM_API int tdm_debug_set(const char *key, int64_t value);
 TDM_API int tdm_debug_get(const char *key, int64_t *value);
 
@@ -230,10 +234,73 @@ TDM_API int tdm_plan_wait_for(tdm_plan *plan, tdm_plan *other);
  * min_margin and freq_offset_hz may be NULL.  Plans with rows_per_chunk > 1 are refused (TDM_ERR_UNSUPPORTED).
  * freq_offset_hz is per carrier and applies to every batch.  Consecutive 256 Ki-sample chunks of one
  * recording are independent (the reference is stateless per read, processor.py:221-273), so a long
- * capture is simply fed as rows of successive batches.                                              */
+ * capture is simply fed as rows of successive batches.  Every call pins, allocates and creates its streams afresh and
+ * needs the whole capture in memory first: a capture loop that reads chunk after chunk is better served by the
+ * persistent tdm_stream below, which sets all of that up once.                                      */
 TDM_API int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, const double *freq_offset_hz,
                                   uint8_t *hard, void *soft, int32_t *n_soft, int32_t *best_phase,
                                   double *min_margin);
+
+/* ---- persistent host-fed stream: the capture loop ---------------------------------------------------
+ * Replaces the reference's read-then-process loop (decrypt_capture.py:101-107 `samples = capture.read_samples(chunk);
+ * processor.process(samples)`, ui/modern.py:1908-1912) for batches of reads: made once per capture, then
+ *     acquire -> fill the returned page-locked input in place (e.g. readinto) -> submit -> ... -> collect (oldest first)
+ * A stream owns `depth` plans of one batch geometry and a ring of `depth` slots, all made by tdm_stream_create: per slot a
+ * device input (zeroed), a library-owned page-locked input (hipHostMalloc), device outputs and page-locked host outputs
+ * (hard, n_soft, best_phase, min_margin; soft only with TDM_STREAM_SOFT); freq_offset_hz / pre_shift_hz are uploaded once.
+ * After create no device or page-locked allocation, registration, stream or event creation happens on the path (a short
+ * read of a length the plan has not seen builds that length's small tables once, as tdm_plan_resize does).
+ *   Placement: step `seq` uses slot seq % depth and runs on that slot's own plan and stream, as
+ *     tetraear_amd.batch.PipelinedBatchDemodulator does with device-resident steps.  One copy stream, shared by the slots,
+ *     carries every host->device copy; a slot's device->host copies follow its kernels on its plan's stream.  Default
+ *     depth 3 = four streams.  All ordering is by events, nothing synchronises the device.
+ *   Ordering and lifetime:
+ *     - tdm_stream_acquire hands out the input of slot seq % depth.  It refuses (TDM_ERR_INVALID) while that slot still
+ *       holds an uncollected result: results are collected in order and at most `depth` steps are outstanding.  Acquiring
+ *       again before a submit returns the same slot.
+ *     - tdm_stream_submit enqueues the acquired slot: its host->device copy waits (on the device) for that slot's previous
+ *       step, the kernels wait for the copy, the outputs are copied back behind the kernels.  Input rows are n_samples
+ *       back to back (the layout of tdm_process with carrier_stride_samples = n_samples); only the first n_valid_inputs
+ *       rows are copied, and the plan rows they do not feed come back with n_soft = 0 (best_phase, min_margin 0).  With
+ *       rows_per_chunk = C one input row feeds C plan rows (plan option "rows_per_chunk").
+ *     - n_samples < chunk (a short last read) is taken in TDM_MODE_REFERENCE: the slot's plan is resized (it is idle, its
+ *       last step was collected) and resized back on the next full read.  The TETRA modes refuse it (TDM_ERR_UNSUPPORTED).
+ *     - tdm_stream_collect returns the OLDEST uncollected step (TDM_ERR_INVALID when none is in flight); wait = 0 returns
+ *       TDM_NOT_READY instead of blocking.  The result's pointers are the slot's page-locked outputs: valid until the slot
+ *       is acquired again (or the stream destroyed).
+ *     - a refused or failed call leaves the ring as it was: the stream stays usable, or can be destroyed.
+ *       tdm_stream_destroy waits for whatever is in flight first.
+ * Every result equals tdm_process of the same batch on a lone plan bit for bit.  Not thread-safe (one caller at a time); a
+ * reader thread may fill an acquired input while the caller's thread collects. */
+#define TDM_STREAM_SOFT 1   /* tdm_stream_create flags: copy the soft symbols back as well */
+typedef struct tdm_stream tdm_stream;
+typedef struct tdm_stream_result {
+    int64_t seq;             /* 0, 1, 2, ... in submission order */
+    int64_t n_samples;       /* samples per input row of this step */
+    int32_t n_rows;          /* plan rows (n_rows of tdm_stream_create) */
+    int32_t n_valid_rows;    /* n_valid_inputs x rows_per_chunk: the rows with symbols */
+    int32_t max_soft;        /* row pitch of hard / soft for this step's length */
+    int32_t soft_bytes;      /* bytes per soft symbol (16 c128, 8 cf32 in the TETRA modes); 0 without TDM_STREAM_SOFT */
+    const uint8_t *hard;     /* [n_rows][max_soft] */
+    const void *soft;        /* [n_rows][max_soft], or NULL without TDM_STREAM_SOFT */
+    const int32_t *n_soft;   /* [n_rows] */
+    const int32_t *best_phase;
+    const double *min_margin;
+} tdm_stream_result;
+/* sample_rate, n_samples (the chunk: samples per input row), n_rows (plan rows), in_fmt, mode: as tdm_plan_create;
+ * depth >= 1 (slots = plans); freq_offset_hz / pre_shift_hz [n_rows] or NULL (pre_shift_hz: TDM_MODE_REFERENCE only);
+ * rows_per_chunk: 1, or C dividing n_rows (TDM_MODE_REFERENCE).  Arguments are checked before any HIP call. */
+TDM_API int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int32_t in_fmt, int32_t mode,
+                              int32_t depth, int32_t flags, const double *freq_offset_hz, const double *pre_shift_hz,
+                              int32_t rows_per_chunk, int32_t device, tdm_stream **out);
+TDM_API int tdm_stream_destroy(tdm_stream *s);
+TDM_API int tdm_stream_acquire(tdm_stream *s, void **iq, int64_t *seq);
+TDM_API int tdm_stream_submit(tdm_stream *s, int64_t n_samples, int32_t n_valid_inputs);
+TDM_API int tdm_stream_collect(tdm_stream *s, int32_t wait, tdm_stream_result *r);
+/* Measured host link of the box: hipMemcpyAsync between a hipHostMalloc buffer of `bytes` and device memory (use 1 GiB or
+ * more), `reps` timed copies after 2, HIP events.  gbs[0] = host->device, gbs[1] = device->host, gbs[2] = both directions at
+ * once (half the buffer each way, the sum of the two), in GB/s. */
+TDM_API int tdm_link_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs);
 
 /* ---- the other public methods of SignalProcessor, one call each (host pointers, blocking) ---
  * All take/return c128 host arrays.                                                          */

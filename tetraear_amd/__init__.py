@@ -3,6 +3,7 @@
     from tetraear_amd.signal import SignalProcessor      # drop-in for tetraear.signal.SignalProcessor
     from tetraear_amd.batch import BatchDemodulator      # many carriers per call, device-resident
     from tetraear_amd.batch import batch_demodulator     # ... with three steps in flight (PipelinedBatchDemodulator)
+    from tetraear_amd.stream import StreamingDemodulator # host-fed capture loop: page-locked slots, copies overlapped
 
 All arithmetic runs in hand-written HIP kernels behind the C-ABI of include/tetrahip.h
 (libtetrahip.so, loaded with ctypes).  There is no CPU compute path.
@@ -16,8 +17,11 @@ def __getattr__(name):
     if name in ("BatchDemodulator", "PipelinedBatchDemodulator", "batch_demodulator"):
         from tetraear_amd import batch
         return getattr(batch, name)
+    if name == "StreamingDemodulator":
+        from tetraear_amd.stream import StreamingDemodulator
+        return StreamingDemodulator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["SignalProcessor", "BatchDemodulator", "PipelinedBatchDemodulator", "batch_demodulator"]
-__version__ = "0.1.2"
+__all__ = ["SignalProcessor", "BatchDemodulator", "PipelinedBatchDemodulator", "batch_demodulator", "StreamingDemodulator"]
+__version__ = "0.1.3"

@@ -29,6 +29,16 @@ class PlanInfo(C.Structure):
                 ("gardner_segments", C.c_int32)]
 
 
+class StreamResult(C.Structure):
+    """tdm_stream_result: pointers into a stream slot's page-locked outputs (valid until the slot is acquired again)"""
+    _fields_ = [("seq", C.c_int64), ("n_samples", C.c_int64), ("n_rows", C.c_int32), ("n_valid_rows", C.c_int32),
+                ("max_soft", C.c_int32), ("soft_bytes", C.c_int32), ("hard", C.c_void_p), ("soft", C.c_void_p),
+                ("n_soft", C.c_void_p), ("best_phase", C.c_void_p), ("min_margin", C.c_void_p)]
+
+
+TDM_ERR_INVALID, TDM_ERR_UNSUPPORTED, TDM_NOT_READY = -1, -5, 1
+STREAM_SOFT = 1     # tdm_stream_create flags: TDM_STREAM_SOFT
+
 _vp, _i32, _i64, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 _P = C.POINTER
 
@@ -50,6 +60,12 @@ SIGNATURES = {
     "tdm_plan_sync": (C.c_int, [_vp]),
     "tdm_plan_wait_for": (C.c_int, [_vp, _vp]),
     "tdm_process_pipelined": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tdm_stream_create": (C.c_int, [_f64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _P(_vp)]),
+    "tdm_stream_destroy": (C.c_int, [_vp]),
+    "tdm_stream_acquire": (C.c_int, [_vp, _P(_vp), _P(_i64)]),
+    "tdm_stream_submit": (C.c_int, [_vp, _i64, _i32]),
+    "tdm_stream_collect": (C.c_int, [_vp, _i32, _P(StreamResult)]),
+    "tdm_link_ceiling": (C.c_int, [_i32, _sz, _i32, _P(_f64)]),
     "tdm_filter_signal": (C.c_int, [_vp, _i64, _f64, _f64, _vp, _P(_i32), _i32]),
     "tdm_frequency_shift": (C.c_int, [_vp, _i64, _f64, _f64, _vp, _i32]),
     "tdm_extract_symbols": (C.c_int, [_vp, _i64, _f64, _f64, _vp, _P(_i64), _P(_i32), _i32]),
@@ -86,7 +102,7 @@ _lib = None
 
 # The header version these bindings (PlanInfo's layout, SIGNATURES) were written for: include/tetrahip.h TDM_VERSION.
 # tests/test_abi_cpu.py holds it to the header; load() holds the library to it.
-ABI_VERSION = 102
+ABI_VERSION = 103
 ALLOW_EXPERIMENT_ENV = "TETRAHIP_ALLOW_EXPERIMENT"   # timing-only builds (negative version): tools/ab_*.py only
 
 

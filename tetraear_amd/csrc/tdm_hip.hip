@@ -29,6 +29,7 @@
 #include "gate_kernels.hpp"
 #include "detect_kernels.hpp"
 #include "occupancy_kernels.hpp"
+#include "stream_ring.hpp"
 
 using namespace tdm;
 
@@ -53,6 +54,7 @@ static DebugSwitch g_debug[] = {
     {"pfb_direct", {0}, 0},              // 1: channeliser plans made from now on use the direct-DFT kernel
     {"pfb_rounds", {0}, 0},              // > 0: rounds per channeliser workgroup (plans made from now on)
     {"gardner_segments", {1}, 1},        // tdm_plan_option "gardner_segments" for TDM_MODE_TETRA_GARDNER plans made from now on (0, 1, K, -1)
+    {"stream_wc", {0}, 0},               // 1: tdm_stream objects made from now on take write-combined page-locked inputs
 };
 static DebugSwitch *debug_find(const char *key)
 {
@@ -1355,6 +1357,256 @@ int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, con
     return TDM_OK;
 }
 
+// ---- persistent host-fed stream (include/tetrahip.h tdm_stream_*): the capture loop with everything made once ------------
+// Slot k = plan k and its stream; one copy stream carries every host->device copy.  Per step: copy stream waits for the
+// slot's previous step (ev_done) -> H2D -> ev_in; plan stream waits ev_in -> kernels -> D2H of the outputs -> ev_done.
+// The host side (stream_ring.hpp) hands a slot out again only after its result was collected, i.e. after ev_done.
+struct StreamSlot {
+    tdm_plan *plan = nullptr;
+    hipStream_t st = nullptr;                // the plan's own stream
+    void *d_iq = nullptr, *h_iq = nullptr;
+    uint8_t *d_hard = nullptr, *h_hard = nullptr;
+    void *d_soft = nullptr, *h_soft = nullptr;
+    int32_t *d_ns = nullptr, *h_ns = nullptr, *d_bp = nullptr, *h_bp = nullptr;
+    double *d_mm = nullptr, *h_mm = nullptr;
+    hipEvent_t ev_in = nullptr, ev_done = nullptr;
+    int64_t n_samples = 0;                   // of the step in the slot
+    int32_t n_valid_rows = 0, max_soft = 0;
+};
+
+struct tdm_stream {
+    int device = 0, rows = 0, rpc = 1, in_rows = 0, fmt = 0, mode = 0, flags = 0;
+    int64_t chunk = 0;
+    int32_t max_soft = 0;                    // at the full chunk: the outputs' capacity per row
+    size_t soft_elem = 0;
+    double *d_foff = nullptr, *d_pre = nullptr;   // per plan row, read by every slot's plan
+    hipStream_t s_h2d = nullptr;
+    std::vector<StreamSlot> slots;
+    StreamRing ring;
+};
+
+static void stream_free(tdm_stream *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->s_h2d) (void)hipStreamSynchronize(s->s_h2d);
+    for (auto &x : s->slots)
+        if (x.st) (void)hipStreamSynchronize(x.st);
+    for (auto &x : s->slots) {
+        void *dev[] = {x.d_iq, x.d_hard, x.d_soft, x.d_ns, x.d_bp, x.d_mm};
+        for (void *q : dev) if (q) (void)hipFree(q);
+        void *host[] = {x.h_iq, x.h_hard, x.h_soft, x.h_ns, x.h_bp, x.h_mm};
+        for (void *q : host) if (q) (void)hipHostFree(q);
+        if (x.ev_in) (void)hipEventDestroy(x.ev_in);
+        if (x.ev_done) (void)hipEventDestroy(x.ev_done);
+        if (x.plan) tdm_plan_destroy(x.plan);
+    }
+    if (s->d_foff) (void)hipFree(s->d_foff);
+    if (s->d_pre) (void)hipFree(s->d_pre);
+    if (s->s_h2d) (void)hipStreamDestroy(s->s_h2d);
+    (void)hipGetLastError();
+    delete s;
+}
+
+int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int32_t in_fmt, int32_t mode, int32_t depth,
+                      int32_t flags, const double *freq_offset_hz, const double *pre_shift_hz, int32_t rows_per_chunk,
+                      int32_t device, tdm_stream **out)
+{
+    // every refusal before the first HIP call
+    if (!out) return fail(TDM_ERR_INVALID, "tdm_stream_create: out is null");
+    *out = nullptr;
+    if (depth < 1 || depth > 16) return fail(TDM_ERR_INVALID, "tdm_stream_create: depth 1..16");
+    if (!(sample_rate > 0) || n_samples < 1 || n_samples > (int64_t(1) << 31) || n_rows < 1 || n_rows > 65535)
+        return fail(TDM_ERR_INVALID, "tdm_stream_create: bad sample_rate / n_samples / n_rows (1..65535)");
+    if (in_fmt < 0 || in_fmt > 3) return fail(TDM_ERR_INVALID, "tdm_stream_create: bad in_fmt");
+    if (mode != TDM_MODE_REFERENCE && mode != TDM_MODE_TETRA && mode != TDM_MODE_TETRA_GARDNER)
+        return fail(TDM_ERR_INVALID, "tdm_stream_create: bad mode");
+    if (flags & ~TDM_STREAM_SOFT) return fail(TDM_ERR_INVALID, "tdm_stream_create: unknown flags");
+    if (rows_per_chunk < 1 || n_rows % rows_per_chunk != 0)
+        return fail(TDM_ERR_INVALID, "tdm_stream_create: rows_per_chunk must divide n_rows");
+    if (mode != TDM_MODE_REFERENCE && (pre_shift_hz || freq_offset_hz || rows_per_chunk > 1))
+        return fail(TDM_ERR_UNSUPPORTED, "tdm_stream_create: pre_shift_hz, freq_offset_hz and rows_per_chunk > 1 are reference-mode inputs");
+    int rc = use_device(device);
+    if (rc) return rc;
+    std::unique_ptr<tdm_stream, void (*)(tdm_stream *)> s(new tdm_stream, stream_free);
+    s->device = device;
+    s->rows = n_rows;
+    s->rpc = rows_per_chunk;
+    s->in_rows = n_rows / rows_per_chunk;
+    s->fmt = in_fmt;
+    s->mode = mode;
+    s->flags = flags;
+    s->chunk = n_samples;
+    s->soft_elem = mode != TDM_MODE_REFERENCE ? 2 * sizeof(float) : 2 * sizeof(double);
+    s->ring = StreamRing(depth);
+    s->slots.resize((size_t)depth);
+    for (auto &x : s->slots) {
+        if ((rc = tdm_plan_create(sample_rate, n_samples, n_rows, in_fmt, mode, device, &x.plan))) return rc;
+        if (rows_per_chunk > 1 && (rc = tdm_plan_option(x.plan, "rows_per_chunk", rows_per_chunk))) return rc;
+        x.st = x.plan->stream;
+    }
+    s->max_soft = (int32_t)s->slots[0].plan->h().max_soft;
+    const size_t in_bytes = (size_t)s->in_rows * n_samples * fmt_bytes(in_fmt);
+    const size_t hard_bytes = (size_t)n_rows * s->max_soft, soft_bytes = hard_bytes * s->soft_elem;
+    const unsigned in_flags = debug_value("stream_wc") == 1 ? hipHostMallocWriteCombined : hipHostMallocDefault;
+    for (auto &x : s->slots) {
+        HIP_TRY(hipMalloc(&x.d_iq, in_bytes));
+        HIP_TRY(hipMemset(x.d_iq, 0, in_bytes));
+        HIP_TRY(hipHostMalloc(&x.h_iq, in_bytes, in_flags));
+        std::memset(x.h_iq, 0, in_bytes);
+        HIP_TRY(hipMalloc((void **)&x.d_hard, hard_bytes));
+        HIP_TRY(hipHostMalloc((void **)&x.h_hard, hard_bytes, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(&x.d_soft, soft_bytes));
+        if (flags & TDM_STREAM_SOFT) HIP_TRY(hipHostMalloc(&x.h_soft, soft_bytes, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&x.d_ns, n_rows * sizeof(int32_t)));
+        HIP_TRY(hipMalloc((void **)&x.d_bp, n_rows * sizeof(int32_t)));
+        HIP_TRY(hipMalloc((void **)&x.d_mm, n_rows * sizeof(double)));
+        HIP_TRY(hipHostMalloc((void **)&x.h_ns, n_rows * sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&x.h_bp, n_rows * sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&x.h_mm, n_rows * sizeof(double), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&x.ev_in, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&x.ev_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(x.ev_done, x.st));   // (the first step's copy then waits for nothing)
+    }
+    if (freq_offset_hz) {
+        HIP_TRY(hipMalloc((void **)&s->d_foff, n_rows * sizeof(double)));
+        HIP_TRY(hipMemcpy(s->d_foff, freq_offset_hz, n_rows * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (pre_shift_hz) {
+        HIP_TRY(hipMalloc((void **)&s->d_pre, n_rows * sizeof(double)));
+        HIP_TRY(hipMemcpy(s->d_pre, pre_shift_hz, n_rows * sizeof(double), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&s->s_h2d, hipStreamNonBlocking));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // (create only: the zeroing above is done before the first step's copy)
+    *out = s.release();
+    return TDM_OK;
+}
+
+int tdm_stream_destroy(tdm_stream *s)
+{
+    stream_free(s);
+    return TDM_OK;
+}
+
+int tdm_stream_acquire(tdm_stream *s, void **iq, int64_t *seq)
+{
+    if (!s || !iq) return fail(TDM_ERR_INVALID, "tdm_stream_acquire: null argument");
+    int k = -1;
+    int64_t q = 0;
+    const char *why = nullptr;
+    if (s->ring.acquire(&k, &q, &why)) return fail(TDM_ERR_INVALID, why);
+    // (collected means waited for: ev_done has completed and nothing reads this input any more; the wait below costs
+    //  nothing then and keeps the rule even after a submit that failed half-way)
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventSynchronize(s->slots[(size_t)k].ev_done));
+    *iq = s->slots[(size_t)k].h_iq;
+    if (seq) *seq = q;
+    return TDM_OK;
+}
+
+int tdm_stream_submit(tdm_stream *s, int64_t n_samples, int32_t n_valid_inputs)
+{
+    if (!s) return fail(TDM_ERR_INVALID, "tdm_stream_submit: null stream");
+    const int k = s->ring.submit_slot();
+    if (k < 0) return fail(TDM_ERR_INVALID, "tdm_stream_submit: no slot acquired (tdm_stream_acquire first)");
+    if (n_samples < 1 || n_samples > s->chunk) return fail(TDM_ERR_INVALID, "tdm_stream_submit: n_samples must be 1..the stream's chunk");
+    if (n_valid_inputs < 1 || n_valid_inputs > s->in_rows)
+        return fail(TDM_ERR_INVALID, "tdm_stream_submit: n_valid_inputs must be 1..the input rows of a batch (n_rows / rows_per_chunk)");
+    if (n_samples != s->chunk && s->mode != TDM_MODE_REFERENCE)
+        return fail(TDM_ERR_UNSUPPORTED, "tdm_stream_submit: a short read needs a reference-mode stream (TETRA-mode plans have one chunk length)");
+    StreamSlot &x = s->slots[(size_t)k];
+    HIP_TRY(hipSetDevice(s->device));
+    // (reference mode: a no-op at the plan's length; the plan is idle, its last step was collected.  TETRA modes: full reads only)
+    int rc = s->mode == TDM_MODE_REFERENCE ? tdm_plan_resize(x.plan, n_samples) : TDM_OK;
+    if (rc) return rc;
+    const int32_t ms = (int32_t)x.plan->h().max_soft;
+    if (ms > s->max_soft) {
+        (void)tdm_plan_resize(x.plan, s->chunk);
+        return fail(TDM_ERR_UNSUPPORTED, "tdm_stream_submit: this read length needs more symbol room per row than the chunk's");
+    }
+    const int32_t valid_rows = n_valid_inputs * s->rpc;
+    const size_t bytes = (size_t)n_valid_inputs * n_samples * fmt_bytes(s->fmt), hard_bytes = (size_t)s->rows * ms;
+    // on a failure after something was enqueued: wait for it, so that the slot's buffers are idle again (the ring is unchanged
+    // and the slot stays acquired)
+#define STREAM_TRY(expr)                                                                   \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            (void)hipGetLastError();                                                       \
+            rc = fail(TDM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+            (void)hipStreamSynchronize(s->s_h2d);                                          \
+            (void)hipStreamSynchronize(x.st);                                              \
+            (void)hipGetLastError();                                                       \
+            return rc;                                                                     \
+        }                                                                                  \
+    } while (0)
+    STREAM_TRY(hipStreamWaitEvent(s->s_h2d, x.ev_done, 0));   // the slot's previous step no longer reads its device input
+    STREAM_TRY(hipMemcpyAsync(x.d_iq, x.h_iq, bytes, hipMemcpyHostToDevice, s->s_h2d));
+    STREAM_TRY(hipEventRecord(x.ev_in, s->s_h2d));
+    STREAM_TRY(hipStreamWaitEvent(x.st, x.ev_in, 0));
+    STREAM_TRY(hipMemsetAsync(x.d_hard, 0, hard_bytes, x.st));   // (as tdm_process: hard beyond n_hard is 0)
+    rc = tdm_process_device(x.plan, x.d_iq, n_samples, s->d_pre, s->d_foff, x.d_hard, (double *)x.d_soft, x.d_ns, x.d_bp,
+                            x.d_mm, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(s->s_h2d);
+        (void)hipStreamSynchronize(x.st);
+        (void)hipGetLastError();
+        return rc;
+    }
+    if (valid_rows < s->rows) {
+        const size_t rest = (size_t)(s->rows - valid_rows);
+        STREAM_TRY(hipMemsetAsync(x.d_ns + valid_rows, 0, rest * sizeof(int32_t), x.st));
+        STREAM_TRY(hipMemsetAsync(x.d_bp + valid_rows, 0, rest * sizeof(int32_t), x.st));
+        STREAM_TRY(hipMemsetAsync(x.d_mm + valid_rows, 0, rest * sizeof(double), x.st));
+    }
+    STREAM_TRY(hipMemcpyAsync(x.h_hard, x.d_hard, hard_bytes, hipMemcpyDeviceToHost, x.st));
+    if (x.h_soft) STREAM_TRY(hipMemcpyAsync(x.h_soft, x.d_soft, hard_bytes * s->soft_elem, hipMemcpyDeviceToHost, x.st));
+    STREAM_TRY(hipMemcpyAsync(x.h_ns, x.d_ns, s->rows * sizeof(int32_t), hipMemcpyDeviceToHost, x.st));
+    STREAM_TRY(hipMemcpyAsync(x.h_bp, x.d_bp, s->rows * sizeof(int32_t), hipMemcpyDeviceToHost, x.st));
+    STREAM_TRY(hipMemcpyAsync(x.h_mm, x.d_mm, s->rows * sizeof(double), hipMemcpyDeviceToHost, x.st));
+    STREAM_TRY(hipEventRecord(x.ev_done, x.st));
+#undef STREAM_TRY
+    x.n_samples = n_samples;
+    x.n_valid_rows = valid_rows;
+    x.max_soft = ms;
+    s->ring.commit_submit();
+    return TDM_OK;
+}
+
+int tdm_stream_collect(tdm_stream *s, int32_t wait, tdm_stream_result *r)
+{
+    if (!s || !r) return fail(TDM_ERR_INVALID, "tdm_stream_collect: null argument");
+    const int k = s->ring.collect_slot();
+    if (k < 0) return fail(TDM_ERR_INVALID, "tdm_stream_collect: nothing in flight");
+    StreamSlot &x = s->slots[(size_t)k];
+    HIP_TRY(hipSetDevice(s->device));
+    if (!wait) {
+        const hipError_t e = hipEventQuery(x.ev_done);
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            g_err = "tdm_stream_collect: the oldest step has not finished";
+            return TDM_NOT_READY;
+        }
+        HIP_TRY(e);
+    } else {
+        HIP_TRY(hipEventSynchronize(x.ev_done));
+    }
+    std::memset(r, 0, sizeof(*r));
+    r->seq = s->ring.next_collect;
+    r->n_samples = x.n_samples;
+    r->n_rows = s->rows;
+    r->n_valid_rows = x.n_valid_rows;
+    r->max_soft = x.max_soft;
+    r->soft_bytes = x.h_soft ? (int32_t)s->soft_elem : 0;
+    r->hard = x.h_hard;
+    r->soft = x.h_soft;
+    r->n_soft = x.h_ns;
+    r->best_phase = x.h_bp;
+    r->min_margin = x.h_mm;
+    s->ring.commit_collect();
+    return TDM_OK;
+}
+
 // ---- timing -----------------------------------------------------------------------------------
 int tdm_plan_time_begin(tdm_plan *plan)
 {
@@ -1538,6 +1790,71 @@ int tdm_hbm_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs)
     (void)hipFree(a);
     (void)hipFree(b);
     if (err != hipSuccess) return fail(TDM_ERR_HIP, std::string("tdm_hbm_ceiling: ") + hipGetErrorString(err));
+    return TDM_OK;
+}
+
+// ---- measured host link (the denominator of the host-fed figures: tools/host_fed_bench.py) ------------------------------
+int tdm_link_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs)
+{
+    if (!gbs || reps < 1 || bytes < (1u << 20)) return fail(TDM_ERR_INVALID, "tdm_link_ceiling: gbs[3], reps >= 1, bytes >= 1 MiB");
+    int rc = use_device(device);
+    if (rc) return rc;
+    bytes &= ~(size_t)4095;
+    void *h = nullptr, *d = nullptr;
+    hipStream_t s0 = nullptr, s1 = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    auto release = [&]() {
+        if (s0) (void)hipStreamSynchronize(s0);
+        if (s1) (void)hipStreamSynchronize(s1);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (e2) (void)hipEventDestroy(e2);
+        if (s0) (void)hipStreamDestroy(s0);
+        if (s1) (void)hipStreamDestroy(s1);
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        (void)hipGetLastError();
+    };
+    hipError_t err = hipHostMalloc(&h, bytes, hipHostMallocDefault);
+    if (err == hipSuccess) err = hipMalloc(&d, bytes);
+    if (err == hipSuccess) err = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipStreamCreateWithFlags(&s1, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipEventCreate(&e0);
+    if (err == hipSuccess) err = hipEventCreate(&e1);
+    if (err == hipSuccess) err = hipEventCreate(&e2);
+    if (err != hipSuccess) {
+        release();
+        return fail(TDM_ERR_NOMEM, std::string("tdm_link_ceiling: ") + hipGetErrorString(err));
+    }
+    std::memset(h, 1, bytes);                 // (every page touched before the first copy)
+    if (err == hipSuccess) err = hipMemset(d, 0, bytes);
+    gbs[0] = gbs[1] = gbs[2] = 0.0;
+    const size_t half = (bytes / 2) & ~(size_t)4095;
+    char *hc = (char *)h, *dc = (char *)d;
+    for (int what = 0; what < 3 && err == hipSuccess; ++what) {
+        auto enqueue = [&]() {
+            if (what == 0) return hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s0);
+            if (what == 1) return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s0);
+            hipError_t e = hipMemcpyAsync(dc, hc, half, hipMemcpyHostToDevice, s0);
+            return e == hipSuccess ? hipMemcpyAsync(hc + half, dc + half, half, hipMemcpyDeviceToHost, s1) : e;
+        };
+        for (int i = 0; i < 2 && err == hipSuccess; ++i) err = enqueue();
+        if (err == hipSuccess) err = hipEventRecord(e0, s0);
+        if (err == hipSuccess) err = hipStreamWaitEvent(s1, e0, 0);
+        for (int i = 0; i < reps && err == hipSuccess; ++i) err = enqueue();
+        if (err == hipSuccess) err = hipEventRecord(e1, s1);
+        if (err == hipSuccess) err = hipStreamWaitEvent(s0, e1, 0);
+        if (err == hipSuccess) err = hipEventRecord(e2, s0);
+        if (err == hipSuccess) err = hipEventSynchronize(e2);
+        float ms = 0.f;
+        if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e2);
+        if (err == hipSuccess && ms > 0.f) {
+            const double moved = (what == 2 ? 2.0 * (double)half : (double)bytes) * reps;
+            gbs[what] = moved / ((double)ms * 1e-3) / 1e9;
+        }
+    }
+    release();
+    if (err != hipSuccess) return fail(TDM_ERR_HIP, std::string("tdm_link_ceiling: ") + hipGetErrorString(err));
     return TDM_OK;
 }
 

@@ -10,6 +10,10 @@ ui/modern.py:1908-1912 reads 128 Ki samples per turn), so a recording is cut int
 reads in memory.  Two page-locked host buffers are filled in turn by a reader thread while the GPU works on the other
 one (rows of a batch = consecutive reads); ONE plan serves the whole recording -- the remainder batch runs on the
 same plan with its unused rows blank, the last, shorter read through tdm_plan_resize.
+
+With `overlapped=True` the same reads go through a StreamingDemodulator (tetraear_amd/stream.py) instead: the reader thread
+fills the next slot's page-locked input in place while the batches before it are copied and demodulated on the device, and
+the per-read yields are the same.
 """
 import os
 import threading
@@ -19,6 +23,7 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import check, ptr
 from tetraear_amd.batch import BatchDemodulator
+from tetraear_amd.stream import StreamingDemodulator
 
 
 def _open(source):
@@ -51,7 +56,8 @@ def _fill(readinto, view):
     return got
 
 
-def iter_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0, rows_per_batch=64, device=0, pre_shifts=None):
+def iter_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0, rows_per_batch=64, device=0, pre_shifts=None,
+                   overlapped=False):
     """source: path of a cu8 file, an object with readinto() (open file, pipe), or a uint8 array of interleaved I,Q.
     Yields, in order, one uint8 symbol array per read of `chunk` samples -- what process() returned per read in the
     reference's loop -- and last the shorter final read, if the recording does not end on a read boundary.
@@ -59,7 +65,13 @@ def iter_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0,
     pre_shifts (a list of C input-rate offsets in Hz): the recording is a wideband stream with C carriers in it -- BASELINE
     config 3 read chunk after chunk.  Every read is then demodulated C times, once per carrier, as the reference's
     `p.process(p.frequency_shift(samples, f_k), freq_offset)` would, `rows_per_batch` reads x C carriers per call (plan option
-    rows_per_chunk), and what is yielded per read is a LIST of C symbol arrays."""
+    rows_per_chunk), and what is yielded per read is a LIST of C symbol arrays.
+
+    overlapped=True: the batches go through a StreamingDemodulator (three slots): host->device copies and kernels of earlier
+    batches run while the reader thread fills the next slot in place; the yields are the same."""
+    if overlapped:
+        yield from _iter_overlapped(source, sample_rate, chunk, freq_offset, rows_per_batch, device, pre_shifts)
+        return
     readinto, close = _open(source)
     lib = _lib.load()
     rows = int(rows_per_batch)
@@ -137,7 +149,99 @@ def iter_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0,
             close()
 
 
-def demodulate_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0, rows_per_batch=64, device=0, pre_shifts=None):
+def _iter_overlapped(source, sample_rate, chunk, freq_offset, rows_per_batch, device, pre_shifts, depth=3):
+    """iter_recording on a StreamingDemodulator: batch b is read into slot b's page-locked input by a reader thread while the
+    batches before it are on the device; results are collected in order and yielded read by read.  A batch of fewer reads
+    submits only its reads (the rows behind them are neither filled nor copied); the last, shorter read is a short submit of
+    one input row in a slot of its own."""
+    rows = int(rows_per_batch)
+    ncar = 0 if pre_shifts is None else len(pre_shifts)
+    rpc = max(ncar, 1)
+    batch_bytes = 2 * chunk * rows
+    readinto, close = _open(source)
+    sd = None
+    t = None     # the reader thread in flight, if any (joined before the stream goes away, also when the consumer stops early)
+    try:
+        sd = StreamingDemodulator(sample_rate, chunk, rows * rpc, "cu8", depth=depth,
+                                  freq_offsets=[float(freq_offset)] * (rows * rpc),
+                                  pre_shifts=None if not ncar else np.tile(np.asarray(pre_shifts, dtype=np.float64), rows),
+                                  rows_per_chunk=rpc, device=device)
+        pending = []      # reads of the submitted steps, oldest first
+        state = {"got": 0, "err": None}
+
+        def read_into(view, owner=None):     # (owner: the stream, kept alive by the thread while it writes into its slot)
+            try:
+                state["got"] = _fill(readinto, memoryview(view))
+            except Exception as e:  # noqa: BLE001 -- re-raised by the consumer
+                state["err"] = e
+                state["got"] = 0
+
+        def results(step_reads):
+            _, hards, _, _, _ = sd.collect()
+            for r in range(step_reads):
+                yield hards[r] if not ncar else hards[r * ncar:(r + 1) * ncar]
+
+        def room():
+            # the next slot is handed out only after its last result was collected: collect (and yield) the oldest first
+            if len(pending) == sd.depth:
+                yield from results(pending.pop(0))
+
+        buf = sd.input_buffer().view(np.uint8)
+        read_into(buf)
+        while True:
+            if state["err"]:
+                raise state["err"]
+            got = state["got"]
+            if got == 0:
+                break
+            n_reads, tail = divmod(got // 2, chunk)
+            seg = None
+            if n_reads:
+                if tail:
+                    seg = buf[2 * chunk * n_reads: 2 * (chunk * n_reads + tail)].copy()
+                sd.submit(chunk, n_reads)
+                pending.append(n_reads)
+            if tail:
+                # the last, shorter read of the recording: one input row of `tail` samples
+                if seg is not None:
+                    yield from room()
+                    buf = sd.input_buffer().view(np.uint8)
+                    buf[:2 * tail] = seg
+                sd.submit(tail, 1)
+                pending.append(1)
+            if got < batch_bytes:
+                break                            # (a short batch means the source has ended)
+            yield from room()
+            buf = sd.input_buffer().view(np.uint8)
+            t = threading.Thread(target=read_into, args=(buf, sd), daemon=True)
+            t.start()
+            while pending:                       # results that are ready already go out while the reader reads
+                out = sd.collect(wait=False)
+                if out is None:
+                    break
+                hards = out[1]
+                for r in range(pending.pop(0)):
+                    yield hards[r] if not ncar else hards[r * ncar:(r + 1) * ncar]
+            t.join()
+            t = None
+        while pending:
+            yield from results(pending.pop(0))
+    finally:
+        # the consumer stopped early (or an error): the reader thread may sit in a pipe read that never returns.  It is a
+        # daemon; it gets a moment to finish, and if it does not, the stream whose page-locked input it writes into is left
+        # alive (held by the thread's closure) rather than freed under it.
+        stuck = False
+        if t is not None:
+            t.join(2.0)
+            stuck = t.is_alive()
+        if not stuck:
+            if sd is not None:
+                sd.close()
+            close()
+
+
+def demodulate_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0, rows_per_batch=64, device=0, pre_shifts=None,
+                         overlapped=False):
     """the whole recording at once: a list with one uint8 symbol array (or, with pre_shifts, one list of them) per read (see
     iter_recording)"""
-    return list(iter_recording(source, sample_rate, chunk, freq_offset, rows_per_batch, device, pre_shifts))
+    return list(iter_recording(source, sample_rate, chunk, freq_offset, rows_per_batch, device, pre_shifts, overlapped))
