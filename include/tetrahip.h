@@ -364,10 +364,42 @@ TDM_API int tdm_channelise(const void *iq, int32_t in_fmt, int64_t n_in, int32_t
                            int64_t *n_out, int32_t device_pointers, int32_t device);
 /* n_streams independent streams in one launch: iq [n_streams][n_in], out [n_streams][M][out_pitch]
  * (out_pitch = row pitch in complex samples, >= n_out; 0 = n_out).  A pitch that is a multiple of 16
- * keeps every 128-byte store of the kernel inside one cache line (1.5x the dense layout's rate).      */
+ * keeps every 128-byte store of the kernel inside one cache line (1.5x the dense layout's rate).
+ * Both calls start every stream COLD: x[n] = 0 before the call's first sample and the output instants m*D count from it,
+ * so channelising a long capture read by read this way glitches at every seam (zeros instead of the previous read, a
+ * jump of the decimation grid and of each channel's phase).  tdm_channeliser below carries the state across reads.    */
 TDM_API int tdm_channelise_batch(const void *iq, int32_t in_fmt, int64_t n_in, int32_t n_streams, int32_t M,
                                  int32_t D, float *out, int64_t out_pitch, int64_t *n_out,
                                  int32_t device_pointers, int32_t device);
+
+/* ---- stateful channeliser: continuous wideband IQ read by read (no counterpart in the reference) ---------------------
+ * Replaces tdm_channelise_batch in a capture loop (the reference reads fixed-size chunks, ui/modern.py:1908-1912): the
+ * object keeps, per stream, the last L-1 = 3M-1 input samples (in wire format) and the stream's position, so that the
+ * outputs of consecutive pushes, concatenated along time, equal ONE tdm_channelise_batch over the concatenated input, bit
+ * for bit (output m of a stream sits at its absolute input instant m*D; oracle/pfb_np.py over the whole stream).
+ *   create    M, in_fmt (cu8 / cs8 / cf32), kernel choice as tdm_channelise_batch; every stream of the object advances
+ *             by the same n_in per push, n_in <= max_n_in.  Checks its arguments before any HIP call and allocates
+ *             everything (history, host-form staging sized by max_n_in); a push allocates nothing.
+ *   push      iq [n_streams][n_in] back to back, out [n_streams][M][out_pitch] cf32 with out_pitch >= ceil(n_in/D), the
+ *             most one push can emit (0 = this push's n_out, dense); *n_out = ceil((pos+n_in)/D) - ceil(pos/D) outputs
+ *             were written (may be 0; pos = samples pushed before).  n_in = 0 is a no-op.  device_pointers = 0: host
+ *             buffers, blocks.  device_pointers != 0: device buffers, enqueued on the calling thread's current stream
+ *             (tdm_set_stream) and returns.  Pushes are ordered among themselves on the device whatever stream each
+ *             ran on (each waits for the previous one's event); the caller orders its own use of iq / out.
+ *   reset     back to a fresh stream (position 0, no history).   position: samples pushed / outputs emitted per stream.
+ *   destroy   waits for the last push first.
+ * Not thread-safe (one caller at a time), like a plan.                                                                 */
+typedef struct tdm_channeliser tdm_channeliser;
+/* replaces: tdm_channelise_batch's per-call set-up (no state) */
+TDM_API int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_streams, int64_t max_n_in,
+                                   int32_t device, tdm_channeliser **out);
+/* replaces: tdm_channelise_batch(iq, in_fmt, n_in, n_streams, M, D, out, out_pitch, n_out, device_pointers, device) */
+TDM_API int tdm_channeliser_push(tdm_channeliser *ch, const void *iq, int64_t n_in, float *out, int64_t out_pitch,
+                                 int64_t *n_out, int32_t device_pointers);
+/* back to a fresh stream (replaces: nothing -- every tdm_channelise_batch call is a fresh stream) */
+TDM_API int tdm_channeliser_reset(tdm_channeliser *ch);
+TDM_API int tdm_channeliser_position(tdm_channeliser *ch, int64_t *samples_in, int64_t *samples_out);
+TDM_API int tdm_channeliser_destroy(tdm_channeliser *ch);
 
 /* ---- occupancy gate of the wideband chain (many-carrier form) ------------------------------------
  * Which channel rows of tdm_channelise_batch's output carry a signal: the decision CaptureThread.run makes before it calls

@@ -80,6 +80,11 @@ SIGNATURES = {
     "tdm_find_sync": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _f64, _i32, _vp, _vp, _vp, _i32, _i32]),
     "tdm_channelise": (C.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _P(_i64), _i32, _i32]),
     "tdm_channelise_batch": (C.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i64), _i32, _i32]),
+    "tdm_channeliser_create": (C.c_int, [_i32, _i32, _i32, _i32, _i64, _i32, _P(_vp)]),
+    "tdm_channeliser_push": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _P(_i64), _i32]),
+    "tdm_channeliser_reset": (C.c_int, [_vp]),
+    "tdm_channeliser_position": (C.c_int, [_vp, _P(_i64), _P(_i64)]),
+    "tdm_channeliser_destroy": (C.c_int, [_vp]),
     "tdm_occupancy_gate": (C.c_int, [_vp, _i64, _i32, _i32, _i64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _i32, _i32]),
     "tdm_process_device_rows": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tdm_hbm_ceiling": (C.c_int, [_i32, _sz, _i32, _P(_f64)]),

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chan_stream.hpp"
 #include "small_dft.hpp"
 
 namespace tdm {
@@ -34,7 +35,25 @@ struct PfbParams {
     int32_t pad2_;
     int64_t in_stride;    // bytes between the input streams of a batch (grid.y)
     int64_t out_batch;    // float2 elements between the outputs of a batch
+    // carried state of a stream (tdm_channeliser, chan_stream.hpp); a stateless call has hist = nullptr and zeros here.
+    // Local input n < 0 reads history slot n + (L-1) when n >= -hist_valid, else zero; output m's window ends at local
+    // input o + m*D, its phase shift is (s_base + m*D) mod M.
+    const void *hist;     // [grid.y] streams of L-1 samples in wire format, hist_stride bytes apart
+    int64_t hist_stride;
+    int64_t hist_valid;
+    int64_t o;
+    int32_t s_base;
+    int32_t pad3_;
 };
+
+// the input format's bytes per sample
+__host__ __device__ constexpr int pfb_fmt_bytes(int fmt) { return fmt == 2 ? 8 : 2; }
+// one past the last history sample of stream y (local index n < 0 lives at byte n * pfb_fmt_bytes from here), or nullptr
+template <int L>
+__device__ __forceinline__ const char *pfb_hist_end(const PfbParams &Q, int y)
+{
+    return Q.hist ? (const char *)Q.hist + (int64_t)y * Q.hist_stride + (int64_t)(L - 1) * pfb_fmt_bytes(Q.fmt) : nullptr;
+}
 
 
 __device__ __forceinline__ float2 pfb_load(const void *iq, int fmt, int64_t n)
@@ -78,11 +97,13 @@ __global__ __launch_bounds__(kPfbThreads) void k_pfb(const void *__restrict__ iq
     const int64_t m0 = (int64_t)blockIdx.x * T;
     iq = (const char *)iq + (int64_t)blockIdx.y * Q.in_stride;
     out += (int64_t)blockIdx.y * Q.out_batch;
-    // ---- stage 0: inputs n = m0*D - (L-1) + i
-    const int64_t nbase = m0 * D - (L - 1);
+    const char *hend = pfb_hist_end<L>(Q, blockIdx.y);
+    // ---- stage 0: inputs n = o + m0*D - (L-1) + i; n < 0 from the history (one load expression for both sources)
+    const int64_t nbase = Q.o + m0 * D - (L - 1);
     for (int i = tid; i < nxs; i += kPfbThreads) {
         const int64_t n = nbase + i;
-        xs[i] = (n >= 0 && n < Q.n_in) ? pfb_load(iq, Q.fmt, n) : make_float2(0.f, 0.f);
+        const bool have = n >= 0 ? n < Q.n_in : n >= -Q.hist_valid;
+        xs[i] = have ? pfb_load(n >= 0 ? iq : (const void *)hend, Q.fmt, n) : make_float2(0.f, 0.f);
     }
     for (int i = tid; i < M1 * M1; i += kPfbThreads) w1[i] = Q.W1[i];
     for (int i = tid; i < M; i += kPfbThreads) wm[i] = Q.WM[i];
@@ -99,7 +120,7 @@ __global__ __launch_bounds__(kPfbThreads) void k_pfb(const void *__restrict__ iq
             acc.x = fmaf(hv, xv.x, acc.x);
             acc.y = fmaf(hv, xv.y, acc.y);
         }
-        const int s = (int)(((m0 + mi) * (int64_t)D) % M);
+        const int s = (int)((Q.s_base + ((m0 + mi) * (int64_t)D) % M) % M);
         int rp = r - s;
         if (rp < 0) rp += M;
         u[mi * RS + rp] = acc;
@@ -155,7 +176,7 @@ template <>
 struct PfbUnit<2> {
     float4 a, b;
     uint32_t ok;
-    __device__ __forceinline__ void load(const char *base, int64_t n0, int64_t n_in)
+    __device__ __forceinline__ void load(const char *base, const char *hend, int64_t hv, int64_t n0, int64_t n_in)
     {
         ok = 0;
         a = b = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -165,11 +186,15 @@ struct PfbUnit<2> {
             __builtin_memcpy(&b, p + 1, 16);
             ok = 15u;
         } else {
-            float2 t0 = make_float2(0.f, 0.f), t1 = t0, t2 = t0, t3 = t0;
-            if (n0 >= 0 && n0 < n_in) t0 = ((const float2 *)base)[n0];
-            if (n0 + 1 >= 0 && n0 + 1 < n_in) t1 = ((const float2 *)base)[n0 + 1];
-            if (n0 + 2 >= 0 && n0 + 2 < n_in) t2 = ((const float2 *)base)[n0 + 2];
-            if (n0 + 3 >= 0 && n0 + 3 < n_in) t3 = ((const float2 *)base)[n0 + 3];
+            // per sample: the push (n >= 0) or the history (-hv <= n < 0), else zero
+            float2 t[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t n = n0 + c;
+                t[c] = make_float2(0.f, 0.f);
+                if (n >= 0 ? n < n_in : n >= -hv) t[c] = ((const float2 *)(n >= 0 ? base : hend))[n];
+            }
+            const float2 t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
             a = make_float4(t0.x, t0.y, t1.x, t1.y);
             b = make_float4(t2.x, t2.y, t3.x, t3.y);
             ok = 15u;   // zeros already in place
@@ -185,7 +210,7 @@ template <int FMT>
 struct PfbUnit {   // cu8 (FMT 0) / cs8 (FMT 1): 8 bytes
     uint2 v;
     uint32_t ok;
-    __device__ __forceinline__ void load(const char *base, int64_t n0, int64_t n_in)
+    __device__ __forceinline__ void load(const char *base, const char *hend, int64_t hv, int64_t n0, int64_t n_in)
     {
         v = make_uint2(0u, 0u);
         if (n0 >= 0 && n0 + 3 < n_in) {
@@ -195,13 +220,15 @@ struct PfbUnit {   // cu8 (FMT 0) / cs8 (FMT 1): 8 bytes
             ok = 0;
             uint32_t w0 = 0u, w1 = 0u;
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (n0 + c >= 0 && n0 + c < n_in) {
-                    const uint32_t h = ((const uint16_t *)base)[n0 + c];
+            for (int c = 0; c < 4; ++c) {
+                const int64_t n = n0 + c;   // the push (n >= 0) or the history (-hv <= n < 0), in wire format either way
+                if (n >= 0 ? n < n_in : n >= -hv) {
+                    const uint32_t h = ((const uint16_t *)(n >= 0 ? base : hend))[n];
                     if (c < 2) w0 |= h << (16 * (c & 1));
                     else w1 |= h << (16 * (c & 1));
                     ok |= 1u << c;
                 }
+            }
             v = make_uint2(w0, w1);
         }
     }
@@ -311,8 +338,9 @@ __device__ __forceinline__ void pfb_pass2(const cf32v *A, cf32v *out, int64_t ou
     }
 }
 
-// NPF: 4-sample units per thread held in registers for the next round; WGS: workgroups per CU aimed at
-template <int M1, int M2, int P, int TB, int FMT, int NPF, int WGS>
+// NPF: 4-sample units per thread held in registers for the next round; WGS: workgroups per CU aimed at;
+// CARRY: reads the carried state of Q (tdm_channeliser).  The stateless instantiation compiles the state away.
+template <int M1, int M2, int P, int TB, int FMT, int NPF, int WGS, bool CARRY>
 __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb_fft(
     const void *__restrict__ iq_, cf32v *__restrict__ out_, int64_t out_stride, const PfbParams Q)
 {
@@ -331,17 +359,19 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
     // (in LDS rather than re-read from memory: loads and stores share vmcnt, so a global load issued after
     //  pass 2's stores would wait for their write acknowledgements)
     const char *iq = (const char *)iq_ + (int64_t)blockIdx.y * Q.in_stride;
+    const char *hend = CARRY ? pfb_hist_end<L>(Q, blockIdx.y) : nullptr;
+    const int64_t hv = CARRY ? Q.hist_valid : 0, o = CARRY ? Q.o : 0;
     cf32v *out = out_ + (int64_t)blockIdx.y * Q.out_batch;
     const int tid = threadIdx.x;
     const int mi = tid / M2, n2 = tid - mi * M2;
     const int k1b = tid / TB, mib = tid - k1b * TB;
-    float hv[NI][P];   // taps of this thread's stage-A branches (the same in every round)
+    float hv_taps[NI][P];   // taps of this thread's stage-A branches (the same in every round)
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
         const int item = tid + it * NT;
         const int r = item - (item / M) * M;
 #pragma unroll
-        for (int p = 0; p < P; ++p) hv[it][p] = Q.h[r + p * M];
+        for (int p = 0; p < P; ++p) hv_taps[it][p] = Q.h[r + p * M];
     }
     for (int i = tid; i < M; i += NT) {
         const float2 w = Q.WM[i];
@@ -351,18 +381,18 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
     PfbUnit<FMT> pf[NPF];
 #pragma unroll
     for (int k = 0; k < NPF; ++k)
-        if (tid + k * NT < nu) pf[k].load(iq, round0 * TB * D - (L - 1) + 4 * (int64_t)(tid + k * NT), Q.n_in);
+        if (tid + k * NT < nu) pf[k].load(iq, hend, hv, o + round0 * TB * D - (L - 1) + 4 * (int64_t)(tid + k * NT), Q.n_in);
     for (int g = 0; g < Q.G; ++g) {
         const int64_t m0 = (round0 + g) * TB;
         if (m0 >= Q.n_out) break;
-        const int64_t nbase = m0 * D - (L - 1);
+        const int64_t nbase = o + m0 * D - (L - 1);
         if (g == 0) {
 #pragma unroll
             for (int k = 0; k < NPF; ++k)
                 if (tid + k * NT < nu) pf[k].store(xs + 4 * (tid + k * NT));
             for (int u = tid + NPF * NT; u < nu; u += NT) {   // windows longer than the prefetch depth
                 PfbUnit<FMT> t;
-                t.load(iq, nbase + 4 * (int64_t)u, Q.n_in);
+                t.load(iq, hend, hv, nbase + 4 * (int64_t)u, Q.n_in);
                 t.store(xs + 4 * u);
             }
         }
@@ -370,9 +400,10 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
         if (g + 1 < Q.G) {
 #pragma unroll
             for (int k = 0; k < NPF; ++k)
-                if (tid + k * NT < nu) pf[k].load(iq, nbase + (int64_t)TB * D + 4 * (int64_t)(tid + k * NT), Q.n_in);
+                if (tid + k * NT < nu) pf[k].load(iq, hend, hv, nbase + (int64_t)TB * D + 4 * (int64_t)(tid + k * NT), Q.n_in);
         }
-        pfb_stage_a<M1, M2, P, TB>(xs, A, hv, tid, D, dmod, (int)((m0 * (int64_t)D) % M));
+        const int s0 = (int)((m0 * (int64_t)D) % M);
+        pfb_stage_a<M1, M2, P, TB>(xs, A, hv_taps, tid, D, dmod, CARRY ? (Q.s_base + s0) % M : s0);
         __syncthreads();
         pfb_pass1<M1, M2>(A, wml, mi, n2);
         __syncthreads();
@@ -385,12 +416,27 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
                 if (tid + k * NT < nu) pf[k].store(xs + 4 * (tid + k * NT));
             for (int u = tid + NPF * NT; u < nu; u += NT) {
                 PfbUnit<FMT> t;
-                t.load(iq, nbase + (int64_t)TB * D + 4 * (int64_t)u, Q.n_in);
+                t.load(iq, hend, hv, nbase + (int64_t)TB * D + 4 * (int64_t)u, Q.n_in);
                 t.store(xs + 4 * u);
             }
         }
         if (tid < TB * M1) pfb_pass2<M1, M2>(A, out, out_stride, m0, Q.n_out, k1b, mib);
     }
+}
+
+// ---- carried state of tdm_channeliser -----------------------------------------------------------------
+// The next history of every stream after a push (chan_stream.hpp chan_hist_source): slot j of new_h = the last L-1 samples
+// of (old_h || this push), copied in wire format (W: uint16_t for cu8 / cs8, uint2 for cf32).  old_h and new_h are two
+// different buffers, so a push shorter than L-1 never shifts a buffer onto itself.  grid.y = stream; strides in samples.
+template <typename W>
+__global__ __launch_bounds__(256) void k_pfb_hist(const W *__restrict__ iq, int64_t in_stride, const W *__restrict__ old_h,
+                                                  W *__restrict__ new_h, int64_t hist_stride, int64_t n_in, int L)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= L - 1) return;
+    const int64_t y = blockIdx.y;
+    const int64_t src = chan_hist_source(j, n_in, L);
+    new_h[y * hist_stride + j] = src >= 0 ? iq[y * in_stride + src] : old_h[y * hist_stride + (-1 - src)];
 }
 
 // (Round 4 also built a half-tile variant for the 8-bit formats -- fp16 window, branch sums fused with a radix-2 split of pass 1,

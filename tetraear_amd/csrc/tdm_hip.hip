@@ -30,6 +30,7 @@
 #include "detect_kernels.hpp"
 #include "occupancy_kernels.hpp"
 #include "stream_ring.hpp"
+#include "chan_stream.hpp"
 
 using namespace tdm;
 
@@ -2477,12 +2478,11 @@ struct PfbTables {
 static std::mutex g_pfb_mu;
 static std::map<std::tuple<int, int, int, int>, PfbTables> g_pfb_cache;  // (device, M1, M2, D) -> tables (kept)
 
-template <int M1, int M2, int P, int TB, int WGS>
-int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 *out, int64_t n_out, int64_t pitch,
-               int n_streams, hipStream_t st, bool sync)
+// prototype and twiddles of (device, M1, M2, D), made once (blocking copies on first use) and kept
+template <int M1, int M2, int P>
+int pfb_tables(int device, int D, PfbTables &tb)
 {
-    constexpr int M = M1 * M2, L = M * P;
-    PfbTables tb;
+    constexpr int M = M1 * M2;
     {
         std::lock_guard<std::mutex> lk(g_pfb_mu);
         auto key = std::make_tuple(device, M1, M2, D);
@@ -2514,7 +2514,41 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
             tb = it->second;
         }
     }
+    return TDM_OK;
+}
+
+// the stream state a launch reads (tdm_channeliser); nullptr = a stateless call (every stream starts cold)
+struct PfbCarry {
+    const void *hist;
+    int64_t hist_stride, hist_valid, o;
+    int32_t s_base;
+};
+
+// LDS of the direct-DFT kernel's tile (the fallback when k_pfb_fft's window does not fit)
+template <int M1, int M2, int P>
+size_t pfb_direct_lds(int D, int T)
+{
+    constexpr int M = M1 * M2, L = M * P;
+    return ((size_t)(T - 1) * D + L + 2 * (size_t)T * (M + 1) + M1 * M1 + M + M2 * M2) * sizeof(float2);
+}
+constexpr int pfb_direct_T(int M) { return M <= 128 ? 32 : 8; }
+
+template <int M1, int M2, int P, int TB, int WGS>
+int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 *out, int64_t n_out, int64_t pitch,
+               int n_streams, hipStream_t st, bool sync, const PfbCarry *carry = nullptr)
+{
+    constexpr int M = M1 * M2, L = M * P;
+    PfbTables tb;
+    int trc = pfb_tables<M1, M2, P>(device, D, tb);
+    if (trc) return trc;
     PfbParams Q{};
+    if (carry) {
+        Q.hist = carry->hist;
+        Q.hist_stride = carry->hist_stride;
+        Q.hist_valid = carry->hist_valid;
+        Q.o = carry->o;
+        Q.s_base = carry->s_base;
+    }
     Q.D = D;
     Q.fmt = fmt;
     Q.n_in = n_in;
@@ -2557,10 +2591,18 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
             const unsigned threads = TB * M2;
             {
                 const bool one = nu <= TB * M2;   // one prefetched unit per thread covers the window
-                switch (fmt) {
-                case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS>; break;
-                case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS>; break;
-                default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS>; break;
+                if (carry) {
+                    switch (fmt) {
+                    case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS, true>; break;
+                    case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS, true>; break;
+                    default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS, true>; break;
+                    }
+                } else {
+                    switch (fmt) {
+                    case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS, false>; break;
+                    case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS, false>; break;
+                    default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS, false>; break;
+                    }
                 }
             }
             HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2571,8 +2613,8 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
             return TDM_OK;
         }
     }
-    Q.T = M <= 128 ? 32 : 8;
-    const size_t lds = ((size_t)(Q.T - 1) * D + L + 2 * (size_t)Q.T * (M + 1) + M1 * M1 + M + M2 * M2) * sizeof(float2);
+    Q.T = pfb_direct_T(M);
+    const size_t lds = pfb_direct_lds<M1, M2, P>(D, Q.T);
     if (lds > 160 * 1024) return fail(TDM_ERR_UNSUPPORTED, "channeliser tile does not fit LDS");
     HIP_TRY(hipFuncSetAttribute((const void *)k_pfb<M1, M2, P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned blocks = (unsigned)((n_out + Q.T - 1) / Q.T);
@@ -2581,6 +2623,57 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
     if (sync) HIP_TRY(hipStreamSynchronize(st));
     return TDM_OK;
 }
+
+// The built filter banks: M -> (M1, M2, P, TB, WGS).  Op::run<M1, M2, P, TB, WGS>() is called for M.
+template <class Op>
+int pfb_for_m(int M, Op &op)
+{
+    switch (M) {
+    case 96: return op.template run<8, 12, 3, 16, 4>();
+    case 72: return op.template run<8, 9, 3, 48, 2>();
+    case 80: return op.template run<8, 10, 3, 32, 3>();
+    case 128: return op.template run<8, 16, 3, 16, 4>();
+    case 400: return op.template run<20, 20, 3, 32, 1>();
+    default: return fail(TDM_ERR_UNSUPPORTED, "channeliser built for M in {72, 80, 96, 128, 400}");
+    }
+}
+struct PfbLaunchOp {
+    int device;
+    const void *iq;
+    int fmt;
+    int64_t n_in;
+    int D;
+    float2 *out;
+    int64_t n_out, pitch;
+    int n_streams;
+    hipStream_t st;
+    bool sync;
+    const PfbCarry *carry;
+    template <int M1, int M2, int P, int TB, int WGS>
+    int run() { return launch_pfb<M1, M2, P, TB, WGS>(device, iq, fmt, n_in, D, out, n_out, pitch, n_streams, st, sync, carry); }
+};
+// host only, no device: does some kernel's tile fit LDS at this D (launch_pfb's choice: k_pfb_fft, else k_pfb)?
+struct PfbFitsOp {
+    int D;
+    template <int M1, int M2, int P, int TB, int WGS>
+    int run()
+    {
+        constexpr int M = M1 * M2;
+        const bool fft = D <= 4 * M && pfb_fft_lds<M1, M2, P, TB>(D) * sizeof(float2) <= 160 * 1024;
+        const bool direct = pfb_direct_lds<M1, M2, P>(D, pfb_direct_T(M)) <= 160 * 1024;
+        return fft || direct ? TDM_OK : fail(TDM_ERR_UNSUPPORTED, "channeliser tile does not fit LDS at this decimation");
+    }
+};
+struct PfbTablesOp {
+    int device, D, L;
+    template <int M1, int M2, int P, int TB, int WGS>
+    int run()
+    {
+        PfbTables tb;
+        L = M1 * M2 * P;
+        return pfb_tables<M1, M2, P>(device, D, tb);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -2607,21 +2700,10 @@ int tdm_channelise_batch(const void *iq, int32_t in_fmt, int64_t n_in, int32_t n
         src = din.p;
         dst = dout.as<float2>();
     }
-    const bool sync = !device_pointers;
-    switch (M) {
-    // device pointers: enqueue on the default stream and return (tdm_dev_sync waits)
-#define TDM_PFB96 16, 4
-#define TDM_PFB72 48, 2
-#define TDM_PFB128 16, 4
-#define TDM_PFB80 32, 3
-    case 96: rc = launch_pfb<8, 12, 3, TDM_PFB96>(device, src, in_fmt, n_in, D, dst, no, pitch, n_streams, device_pointers ? g_cur_stream : nullptr, sync); break;
-    case 72: rc = launch_pfb<8, 9, 3, TDM_PFB72>(device, src, in_fmt, n_in, D, dst, no, pitch, n_streams, device_pointers ? g_cur_stream : nullptr, sync); break;
-    case 80: rc = launch_pfb<8, 10, 3, TDM_PFB80>(device, src, in_fmt, n_in, D, dst, no, pitch, n_streams, device_pointers ? g_cur_stream : nullptr, sync); break;
-    case 128: rc = launch_pfb<8, 16, 3, TDM_PFB128>(device, src, in_fmt, n_in, D, dst, no, pitch, n_streams, device_pointers ? g_cur_stream : nullptr, sync); break;
-    case 400: rc = launch_pfb<20, 20, 3, 32, 1>(device, src, in_fmt, n_in, D, dst, no, pitch, n_streams, device_pointers ? g_cur_stream : nullptr, sync); break;
-    default: return fail(TDM_ERR_UNSUPPORTED, "channeliser built for M in {72, 80, 96, 128, 400}");
-    }
-    if (rc) return rc;
+    // device pointers: enqueue on the current stream and return (tdm_dev_sync waits)
+    PfbLaunchOp op{device, src, in_fmt, n_in, D, dst, no, pitch, n_streams, device_pointers ? g_cur_stream : nullptr,
+                   !device_pointers, nullptr};
+    if ((rc = pfb_for_m(M, op))) return rc;
     if (!device_pointers) HIP_TRY(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));
     return TDM_OK;
 }
@@ -2693,6 +2775,155 @@ int tdm_channelise(const void *iq, int32_t in_fmt, int64_t n_in, int32_t M, int3
                    int32_t device_pointers, int32_t device)
 {
     return tdm_channelise_batch(iq, in_fmt, n_in, 1, M, D, out, 0, n_out, device_pointers, device);
+}
+
+// ---- stateful channeliser (include/tetrahip.h tdm_channeliser_*): consecutive pushes = one call over the whole stream --------
+// Per stream the last L-1 input samples in wire format, in two ping-pong buffers: a push's channeliser reads hist[cur], the
+// history kernel behind it writes hist[cur ^ 1] (chan_stream.hpp says which sample goes where), then cur flips.  Pushes are
+// ordered by ev_last: every push waits for it on its stream and records it behind its own work, whatever stream it ran on.
+struct tdm_channeliser {
+    int device = 0, M = 0, D = 1, L = 1, fmt = 0, n_streams = 1;
+    int64_t max_n_in = 0;
+    int64_t pitch_dev = 0;                   // row pitch of d_out (host-form pushes)
+    int64_t samples_in = 0, samples_out = 0; // per stream, since create / reset
+    void *hist[2] = {nullptr, nullptr};
+    int cur = 0;
+    int64_t hist_stride = 0;                 // bytes between the streams of a history buffer
+    void *d_in = nullptr, *d_out = nullptr;  // host-form staging
+    hipStream_t st = nullptr;                // host-form pushes
+    hipEvent_t ev_last = nullptr;
+};
+
+static void channeliser_free(tdm_channeliser *ch)
+{
+    if (!ch) return;
+    (void)hipSetDevice(ch->device);
+    if (ch->ev_last) (void)hipEventSynchronize(ch->ev_last);
+    if (ch->st) (void)hipStreamSynchronize(ch->st);
+    void *dev[] = {ch->hist[0], ch->hist[1], ch->d_in, ch->d_out};
+    for (void *q : dev) if (q) (void)hipFree(q);
+    if (ch->ev_last) (void)hipEventDestroy(ch->ev_last);
+    if (ch->st) (void)hipStreamDestroy(ch->st);
+    (void)hipGetLastError();
+    delete ch;
+}
+
+int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_streams, int64_t max_n_in, int32_t device,
+                           tdm_channeliser **out)
+{
+    // every refusal before the first HIP call
+    if (!out) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: out is null");
+    *out = nullptr;
+    if (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32)
+        return fail(TDM_ERR_INVALID, "tdm_channeliser_create: in_fmt must be cu8, cs8 or cf32");
+    if (D < 1) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: decimation D < 1");
+    if (n_streams < 1 || n_streams > 65535) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: n_streams 1..65535");
+    if (max_n_in < 1 || max_n_in > (int64_t(1) << 40) / n_streams)
+        return fail(TDM_ERR_INVALID, "tdm_channeliser_create: max_n_in must be 1..2^40 / n_streams");
+    PfbFitsOp fits{D};
+    int rc = pfb_for_m(M, fits);
+    if (rc) return rc;
+    if ((rc = use_device(device))) return rc;
+    std::unique_ptr<tdm_channeliser, void (*)(tdm_channeliser *)> ch(new tdm_channeliser, channeliser_free);
+    ch->device = device;
+    ch->M = M;
+    ch->D = D;
+    ch->fmt = in_fmt;
+    ch->n_streams = n_streams;
+    ch->max_n_in = max_n_in;
+    PfbTablesOp tabs{device, D, 0};
+    if ((rc = pfb_for_m(M, tabs))) return rc;   // (made here: a push allocates nothing)
+    ch->L = tabs.L;
+    const int fb = pfb_fmt_bytes(in_fmt);
+    ch->hist_stride = (int64_t)(ch->L - 1) * fb;
+    ch->pitch_dev = (max_n_in + D - 1) / D;
+    ch->pitch_dev = (ch->pitch_dev + 15) / 16 * 16;
+    const size_t hb = (size_t)n_streams * ch->hist_stride;
+    for (void *&h : ch->hist) {
+        HIP_TRY(hipMalloc(&h, hb));
+        HIP_TRY(hipMemset(h, 0, hb));
+    }
+    HIP_TRY(hipMalloc(&ch->d_in, (size_t)n_streams * max_n_in * fb));
+    HIP_TRY(hipMalloc(&ch->d_out, (size_t)n_streams * M * ch->pitch_dev * sizeof(float2)));
+    HIP_TRY(hipStreamCreateWithFlags(&ch->st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ch->ev_last, hipEventDisableTiming));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // (the zeroing above is done before the first push)
+    HIP_TRY(hipEventRecord(ch->ev_last, ch->st));
+    *out = ch.release();
+    return TDM_OK;
+}
+
+int tdm_channeliser_push(tdm_channeliser *ch, const void *iq, int64_t n_in, float *out, int64_t out_pitch, int64_t *n_out,
+                         int32_t device_pointers)
+{
+    if (!ch || !n_out) return fail(TDM_ERR_INVALID, "tdm_channeliser_push: null channeliser or n_out");
+    *n_out = 0;
+    if (n_in < 0 || n_in > ch->max_n_in) return fail(TDM_ERR_INVALID, "tdm_channeliser_push: n_in must be 0..max_n_in");
+    if (n_in == 0) return TDM_OK;
+    if (!iq || !out) return fail(TDM_ERR_INVALID, "tdm_channeliser_push: null iq or out");
+    const int D = ch->D, M = ch->M;
+    if (out_pitch < 0 || (out_pitch != 0 && out_pitch < (n_in + D - 1) / D))
+        return fail(TDM_ERR_INVALID, "tdm_channeliser_push: out_pitch must hold ceil(n_in / D) (or be 0: this push's n_out)");
+    const ChanPush p = chan_push(ch->samples_in, n_in, M, D, ch->L);
+    const int64_t pitch = out_pitch ? out_pitch : p.n_out;
+    const int fb = pfb_fmt_bytes(ch->fmt);
+    HIP_TRY(hipSetDevice(ch->device));
+    hipStream_t st = device_pointers ? g_cur_stream : ch->st;
+    HIP_TRY(hipStreamWaitEvent(st, ch->ev_last, 0));   // behind the previous push, on whatever stream it ran
+    const void *src = iq;
+    float2 *dst = (float2 *)out;
+    int64_t dpitch = pitch;
+    if (!device_pointers) {
+        HIP_TRY(hipMemcpyAsync(ch->d_in, iq, (size_t)ch->n_streams * n_in * fb, hipMemcpyHostToDevice, st));
+        src = ch->d_in;
+        dst = (float2 *)ch->d_out;
+        dpitch = ch->pitch_dev;
+    }
+    int rc;
+    if (p.n_out > 0) {
+        const PfbCarry carry{ch->hist[ch->cur], ch->hist_stride, p.hist_valid, p.o, p.s_base};
+        PfbLaunchOp op{ch->device, src, ch->fmt, n_in, D, dst, p.n_out, dpitch, ch->n_streams, st, false, &carry};
+        if ((rc = pfb_for_m(M, op))) return rc;
+    }
+    const dim3 hgrid((unsigned)((ch->L - 1 + 255) / 256), (unsigned)ch->n_streams);
+    if (ch->fmt == TDM_CF32)
+        hipLaunchKernelGGL(k_pfb_hist<uint2>, hgrid, dim3(256), 0, st, (const uint2 *)src, n_in, (const uint2 *)ch->hist[ch->cur],
+                           (uint2 *)ch->hist[ch->cur ^ 1], ch->hist_stride / fb, n_in, ch->L);
+    else
+        hipLaunchKernelGGL(k_pfb_hist<uint16_t>, hgrid, dim3(256), 0, st, (const uint16_t *)src, n_in,
+                           (const uint16_t *)ch->hist[ch->cur], (uint16_t *)ch->hist[ch->cur ^ 1], ch->hist_stride / fb, n_in, ch->L);
+    HIP_TRY(hipGetLastError());
+    if (!device_pointers && p.n_out > 0)
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)pitch * sizeof(float2), ch->d_out, (size_t)dpitch * sizeof(float2),
+                                 (size_t)p.n_out * sizeof(float2), (size_t)ch->n_streams * M, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ch->ev_last, st));
+    if (!device_pointers) HIP_TRY(hipStreamSynchronize(st));
+    ch->cur ^= 1;
+    ch->samples_in += n_in;
+    ch->samples_out += p.n_out;
+    *n_out = p.n_out;
+    return TDM_OK;
+}
+
+int tdm_channeliser_reset(tdm_channeliser *ch)
+{
+    if (!ch) return fail(TDM_ERR_INVALID, "tdm_channeliser_reset: null channeliser");
+    ch->samples_in = ch->samples_out = 0;   // hist_valid = 0: the stored history is never read again
+    return TDM_OK;
+}
+
+int tdm_channeliser_position(tdm_channeliser *ch, int64_t *samples_in, int64_t *samples_out)
+{
+    if (!ch || !samples_in || !samples_out) return fail(TDM_ERR_INVALID, "tdm_channeliser_position: null argument");
+    *samples_in = ch->samples_in;
+    *samples_out = ch->samples_out;
+    return TDM_OK;
+}
+
+int tdm_channeliser_destroy(tdm_channeliser *ch)
+{
+    channeliser_free(ch);
+    return TDM_OK;
 }
 
 // ---- introspection (no device needed) -----------------------------------------------------------

@@ -14,6 +14,9 @@ same plan with its unused rows blank, the last, shorter read through tdm_plan_re
 With `overlapped=True` the same reads go through a StreamingDemodulator (tetraear_amd/stream.py) instead: the reader thread
 fills the next slot's page-locked input in place while the batches before it are copied and demodulated on the device, and
 the per-read yields are the same.
+
+`iter_channels` is the wideband side of the loop: the reads of one or more wideband streams go through a
+StreamingChanneliser, which carries the filter bank's state from read to read, and each read's channel block is yielded.
 """
 import os
 import threading
@@ -23,6 +26,8 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import check, ptr
 from tetraear_amd.batch import BatchDemodulator
+from tetraear_amd.channeliser import _FMT_OF as _CHAN_FMT
+from tetraear_amd.channeliser import StreamingChanneliser
 from tetraear_amd.stream import StreamingDemodulator
 
 
@@ -238,6 +243,31 @@ def _iter_overlapped(source, sample_rate, chunk, freq_offset, rows_per_batch, de
             if sd is not None:
                 sd.close()
             close()
+
+
+def iter_channels(source, M, D, chunk, fmt="cu8", streams=1, device=0):
+    """source: path of a wideband IQ file, an object with readinto() (open file, pipe), or an array of its bytes, in the wire
+    format `fmt` (cu8 / cs8 / cf32).  Each read takes `streams` x `chunk` samples, the streams back to back ([streams][chunk]),
+    and yields that read's channel block, complex64 [streams][M][n_out] -- the last, shorter read as it is (its bytes split
+    evenly between the streams).  The blocks go through one StreamingChanneliser, so concatenated along time they equal one
+    channelise_batch call over the whole source; n_out varies from read to read (ceil / floor of chunk / D) and may be 0."""
+    fb = _lib.FMT_BYTES[_CHAN_FMT[fmt]]
+    streams, chunk = int(streams), int(chunk)
+    readinto, close = _open(source)
+    buf = np.empty(streams * chunk * fb, dtype=np.uint8)
+    try:
+        with StreamingChanneliser(M, D, fmt, streams, chunk, device) as ch:
+            while True:
+                got = _fill(readinto, memoryview(buf))
+                if got % (streams * fb):
+                    raise ValueError(f"iter_channels: the source ends inside a sample ({got} bytes in the last read, "
+                                     f"not a multiple of {streams} streams x {fb} bytes)")
+                if got:
+                    yield ch.push(buf[:got])
+                if got < len(buf):
+                    break
+    finally:
+        close()
 
 
 def demodulate_recording(source, sample_rate=2.4e6, chunk=256 * 1024, freq_offset=0.0, rows_per_batch=64, device=0, pre_shifts=None,
