@@ -31,6 +31,7 @@
 #include "occupancy_kernels.hpp"
 #include "stream_ring.hpp"
 #include "chan_stream.hpp"
+#include "hip_owned.hpp"
 
 using namespace tdm;
 
@@ -244,25 +245,20 @@ static const char *kStageNames[ST_COUNT] = {"dec_block", "dec_carry", "dec_fixup
 
 struct StageTimer {
     bool on = false;
-    struct Rec { int stage; hipEvent_t a, b; };
+    struct Rec { int stage; Event a, b; };
     std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
-    hipEvent_t get()
+    std::vector<Event> pool;
+    Event get()
     {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
+        Event e;
+        if (!pool.empty()) { e = std::move(pool.back()); pool.pop_back(); return e; }
+        (void)event_create(e);
         return e;
     }
     void release_all()
     {
-        for (auto &r : recs) { pool.push_back(r.a); pool.push_back(r.b); }
+        for (auto &r : recs) { pool.push_back(std::move(r.a)); pool.push_back(std::move(r.b)); }
         recs.clear();
-    }
-    ~StageTimer()
-    {
-        release_all();
-        for (auto e : pool) (void)hipEventDestroy(e);
     }
 };
 
@@ -273,14 +269,14 @@ struct HipBackend {
     int device = 0;
 
     struct Scope {
-        HipBackend &be; int stage; hipEvent_t a{}, b{}; bool on;
+        HipBackend &be; int stage; Event a, b; bool on;
         Scope(HipBackend &be_, int st) : be(be_), stage(st), on(be_.timer && be_.timer->on)
         {
-            if (on) { a = be.timer->get(); b = be.timer->get(); (void)hipEventRecord(a, be.stream); }
+            if (on) { a = be.timer->get(); b = be.timer->get(); (void)hipEventRecord(a.get(), be.stream); }
         }
         ~Scope()
         {
-            if (on) { (void)hipEventRecord(b, be.stream); be.timer->recs.push_back({stage, a, b}); }
+            if (on) { (void)hipEventRecord(b.get(), be.stream); be.timer->recs.push_back({stage, std::move(a), std::move(b)}); }
             hipError_t e = hipGetLastError();
             if (e != hipSuccess && be.err == hipSuccess) be.err = e;
         }
@@ -409,17 +405,20 @@ static std::vector<double> tetra_rrc_taps(double sps)
 // ------------------------------------------------------------------------------------------
 struct Variant {
     RefPlanHost h;
-    double *d_tab = nullptr;     // the length-dependent tables of every stage, one allocation
+    DevPtr<double> d_tab;        // the length-dependent tables of every stage, one allocation
     ZpParams dec{}, lpf{}, dec_raw{};
     Lp2Params lp2{}, lp2_raw{};
     double *d_y = nullptr, *d_z = nullptr, *d_partials = nullptr;
     uint64_t stamp = 0;          // last use (eviction order)
     uint64_t id = 0;             // unique within the plan
-    ~Variant() { if (d_tab) (void)hipFree(d_tab); }
 };
 
 constexpr size_t kMaxVariants = 32;
 
+static void sync_scratch_release(int device, hipStream_t st);   // (find_sync's per-stream scratch, below)
+
+// Ownership: every device buffer, stream and event of a plan is a member owner (hip_owned.hpp); the destructor's body drains
+// the plan's stream before the members go.
 struct tdm_plan {
     int rows = 0, fmt = 0, mode = 0, device = 0;
     double sample_rate = 0.0;
@@ -430,14 +429,14 @@ struct tdm_plan {
     std::map<int64_t, std::unique_ptr<Variant>> variants;
     Variant *cur = nullptr;
     uint64_t clock = 0;
-    std::map<const ZpSharedTables *, std::pair<std::shared_ptr<const ZpSharedTables>, double *>> d_shared;   // uploaded once per plan
-    double *d_work = nullptr;    // work buffers of the stages, carved per variant, sized for the longest chunk so far
+    std::map<const ZpSharedTables *, std::pair<std::shared_ptr<const ZpSharedTables>, DevPtr<double>>> d_shared;   // uploaded once per plan
+    DevPtr<double> d_work;       // work buffers of the stages, carved per variant, sized for the longest chunk so far
     size_t work_doubles = 0;
     const RefPlanHost &h() const { return cur->h; }
     // TETRA mode
     TetraParams tp{};
-    uint32_t *d_tapops = nullptr;   // TetraParams::tap_ops
-    float2 *d_gy = nullptr;         // TDM_MODE_TETRA_GARDNER, three-launch path only: matched-filter output (allocated the first time that path runs)
+    DevPtr<uint32_t> d_tapops;      // TetraParams::tap_ops
+    DevPtr<float2> d_gy;            // TDM_MODE_TETRA_GARDNER, three-launch path only: matched-filter output (allocated the first time that path runs)
     int64_t gy_pitch = 0;
     int gardner_fused_ok = -1;      // does the fused Gardner kernel serve this plan (tap count, carriers, device)?  -1: not asked yet
     // two segments per carrier (GardnerSeg): geometry and temporaries, made the first time the plan runs that way
@@ -446,21 +445,28 @@ struct tdm_plan {
     int gardner_seg = 0;            // pieces per carrier's chunk (TDM_MODE_TETRA_GARDNER: 1 whole chunks, 2 / 4 / 8: GardnerSeg)
     GardnerSeg gseg{};
     TetraParams gtp{};              // the plan's parameters with a half's length and row capacity
-    float2 *d_gsoft = nullptr;      // [K or K - 1][rows][gtp.max_soft] the pieces' symbols
-    int32_t *d_gint = nullptr;      // [4][K rows]: symbol counts, timing, seam indices (in, out)
-    float *d_gts = nullptr;         // [2][K rows] seam instants (in, out)
+    DevPtr<float2> d_gsoft;         // [K or K - 1][rows][gtp.max_soft] the pieces' symbols
+    DevPtr<int32_t> d_gint;         // [4][K rows]: symbol counts, timing, seam indices (in, out)
+    DevPtr<float> d_gts;            // [2][K rows] seam instants (in, out)
     // staging for the host-pointer entry point
-    void *d_iq = nullptr;
+    DevPtr<void> d_iq;
     size_t d_iq_bytes = 0;
     bool staging_ready = false;
     size_t staging_soft = 0;     // rows * max_soft the staging buffers were sized for
-    double *d_pre = nullptr, *d_foff = nullptr, *d_soft = nullptr, *d_margin = nullptr;
-    uint8_t *d_hard = nullptr;
-    int32_t *d_nsoft = nullptr, *d_bp = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_order = nullptr;   // tdm_plan_wait_for: "everything enqueued on this plan's stream so far" (made on first use)
+    DevPtr<double> d_pre, d_foff, d_soft, d_margin;
+    DevPtr<uint8_t> d_hard;
+    DevPtr<int32_t> d_nsoft, d_bp;
+    Stream stream;
+    Event ev0, ev1;
+    Event ev_order;                  // tdm_plan_wait_for: "everything enqueued on this plan's stream so far" (made on first use)
     StageTimer timer;
+    ~tdm_plan()
+    {
+        (void)hipSetDevice(device);
+        if (!stream) return;
+        (void)hipStreamSynchronize(stream.get());
+        sync_scratch_release(device, stream.get());   // the stream goes away: so does the scratch keyed by it
+    }
 };
 
 static inline size_t even(size_t x) { return (x + 1) & ~(size_t)1; }   // 16-byte granules
@@ -493,13 +499,12 @@ static int shared_on_device(tdm_plan *plan, const std::shared_ptr<const ZpShared
     if (!sh) return TDM_OK;
     auto it = plan->d_shared.find(sh.get());
     if (it == plan->d_shared.end()) {
-        double *d = nullptr;
-        HIP_TRY(hipMalloc(&d, sh->blob.size() * sizeof(double)));
-        hipError_t e = hipMemcpy(d, sh->blob.data(), sh->blob.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(TDM_ERR_HIP, std::string("hipMemcpy(shared tables): ") + hipGetErrorString(e)); }
-        it = plan->d_shared.emplace(sh.get(), std::make_pair(sh, d)).first;
+        DevPtr<double> d;
+        HIP_TRY(dev_alloc(d, sh->blob.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(d.get(), sh->blob.data(), sh->blob.size() * sizeof(double), hipMemcpyHostToDevice));
+        it = plan->d_shared.emplace(sh.get(), std::make_pair(sh, std::move(d))).first;
     }
-    *out = it->second.second;
+    *out = it->second.second.get();
     return TDM_OK;
 }
 
@@ -508,14 +513,8 @@ static int shared_on_device(tdm_plan *plan, const std::shared_ptr<const ZpShared
 // plan's stream has just been synchronised.  The variant under construction holds its tables through its RefPlanHost.
 static void shared_gc(tdm_plan *plan)
 {
-    for (auto it = plan->d_shared.begin(); it != plan->d_shared.end();) {
-        if (it->second.first.use_count() == 1) {
-            (void)hipFree(it->second.second);
-            it = plan->d_shared.erase(it);
-        } else {
-            ++it;
-        }
-    }
+    for (auto it = plan->d_shared.begin(); it != plan->d_shared.end();)
+        it = it->second.first.use_count() == 1 ? plan->d_shared.erase(it) : std::next(it);
 }
 
 static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
@@ -547,24 +546,25 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
     const size_t o_rc = h.raw_S ? put(h.lp2_raw.cst) : 0, o_rs = h.raw_S ? put(h.lp2_raw.seeds) : 0;
     const size_t o_li = h.lp2.ok ? put(h.lp2.items) : 0, o_ri = h.raw_S ? put(h.lp2_raw.items) : 0;
     if (!tab.empty()) {
-        HIP_TRY(hipMalloc(&v->d_tab, tab.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(v->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(v->d_tab, tab.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(v->d_tab.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     }
+    double *const d_tab = v->d_tab.get();
     int rc;
     const double *sb = nullptr;
     if (h.decimated) {
         if ((rc = shared_on_device(plan, h.dec.shared, &sb))) return rc;
         v->dec = h.dec.p;
-        h.dec.bind(v->dec, v->d_tab + o_dec, sb);
+        h.dec.bind(v->dec, d_tab + o_dec, sb);
     }
     if (use_lpf) {
         v->lpf = h.lpf_t.p;
-        h.lpf_t.bind(v->lpf, v->d_tab + o_lpf);
+        h.lpf_t.bind(v->lpf, d_tab + o_lpf);
     }
     if (h.raw_S) {
         if ((rc = shared_on_device(plan, h.dec_raw.shared, &sb))) return rc;
         v->dec_raw = h.dec_raw.p;
-        h.dec_raw.bind(v->dec_raw, v->d_tab + o_raw, sb);
+        h.dec_raw.bind(v->dec_raw, d_tab + o_raw, sb);
     }
     // ---- work: carved out of one buffer that only grows
     // y: the low-rate signal when nothing downstream forms it on the fly (no decimation, or no channel filter);
@@ -581,23 +581,19 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
     if (need > plan->work_doubles) {
         // the new buffer first: if the allocation fails the plan keeps serving the lengths it has.  Then: kernels of
         // earlier calls may still be using the old buffer, and the other variants' pointers into it go stale
-        double *grown = nullptr;
-        if (hipMalloc(&grown, need * sizeof(double)) != hipSuccess) {
+        DevPtr<double> grown;
+        if (dev_alloc(grown, need * sizeof(double)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(TDM_ERR_NOMEM, "plan work buffer: hipMalloc of " + std::to_string(need * sizeof(double)) + " bytes failed");
         }
-        if (hipStreamSynchronize(plan->stream) != hipSuccess) {
-            (void)hipFree(grown);
-            return fail(TDM_ERR_HIP, "hipStreamSynchronize(plan->stream)");
-        }
+        if (hipStreamSynchronize(plan->stream.get()) != hipSuccess) return fail(TDM_ERR_HIP, "hipStreamSynchronize(plan->stream)");
         plan->cur = nullptr;
         plan->variants.clear();
         shared_gc(plan);
-        if (plan->d_work) (void)hipFree(plan->d_work);
-        plan->d_work = grown;
+        plan->d_work = std::move(grown);
         plan->work_doubles = need;
     }
-    double *w = plan->d_work;
+    double *w = plan->d_work.get();
     if (h.decimated) w = zp_bind_work(v->dec, rows, w);
     if (use_lpf) w = zp_bind_work(v->lpf, rows, w);
     if (h.raw_S) w = zp_bind_work(v->dec_raw, rows, w);
@@ -605,10 +601,10 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
         v->lp2 = h.lp2.p;
         v->lp2.zt = w; w += n_zt;
         v->lp2.partials = w; w += n_lp2p;
-        v->lp2.lane_m = v->d_tab + o_lm;
-        v->lp2.cst = v->d_tab + o_lc;
-        if (!h.lp2.seeds.empty()) v->lp2.seeds = v->d_tab + o_ls;
-        if (!h.lp2.items.empty()) v->lp2.items = (const int32_t *)(v->d_tab + o_li);
+        v->lp2.lane_m = d_tab + o_lm;
+        v->lp2.cst = d_tab + o_lc;
+        if (!h.lp2.seeds.empty()) v->lp2.seeds = d_tab + o_ls;
+        if (!h.lp2.items.empty()) v->lp2.items = (const int32_t *)(d_tab + o_li);
         if (h.raw_S) {
             // the raw-integer decimator's geometry: own tables and work buffers, same low-rate outputs
             // (the edge constants depend on the lane grid's offset, which follows the decimator's block geometry)
@@ -616,9 +612,9 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
             v->lp2_raw.zt = v->lp2.zt;
             v->lp2_raw.partials = v->lp2.partials;
             v->lp2_raw.lane_m = v->lp2.lane_m;
-            v->lp2_raw.cst = v->d_tab + o_rc;
-            v->lp2_raw.seeds = v->d_tab + o_rs;
-            v->lp2_raw.items = (const int32_t *)(v->d_tab + o_ri);
+            v->lp2_raw.cst = d_tab + o_rc;
+            v->lp2_raw.seeds = d_tab + o_rs;
+            v->lp2_raw.items = (const int32_t *)(d_tab + o_ri);
         }
     }
     if (need_y) { v->d_y = w; w += nd; }
@@ -630,7 +626,7 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
         for (auto it = plan->variants.begin(); it != plan->variants.end(); ++it)
             if (it->second->stamp < old->second->stamp) old = it;
         // (its tables may still be read by kernels in flight)
-        HIP_TRY(hipStreamSynchronize(plan->stream));
+        HIP_TRY(hipStreamSynchronize(plan->stream.get()));
         plan->variants.erase(old);
         shared_gc(plan);
     }
@@ -644,8 +640,6 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
 
 static size_t fmt_bytes(int fmt) { return fmt == TDM_CU8 || fmt == TDM_CS8 ? 2 : (fmt == TDM_CF32 ? 8 : 16); }
 static int tetra_fmt8(int fmt) { return fmt == TDM_CU8 ? 1 : (fmt == TDM_CS8 ? 2 : 0); }   // the TETRA-mode kernels' FMT8
-
-static void sync_scratch_release(int device, hipStream_t st);   // (find_sync's per-stream scratch, below)
 
 // Geometry of a chunk walked in K pieces (oracle/tetra_np.py gardner_segments is the same arithmetic): false when the chunk is
 // too short (a piece's own part, n / K, under 1.9 warm-ups)
@@ -682,10 +676,9 @@ static bool gardner_geometry(int64_t n, double sps, int ntaps_design, int K, Gar
 static int gardner_choose_pieces(tdm_plan *p, long long allow)
 {
     const TetraParams &tp = p->tp;
-    for (void **q : {(void **)&p->d_gsoft, (void **)&p->d_gint, (void **)&p->d_gts}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
+    p->d_gsoft.reset();
+    p->d_gint.reset();
+    p->d_gts.reset();
     p->gseg = GardnerSeg{};
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
@@ -727,44 +720,26 @@ static int gardner_choose_pieces(tdm_plan *p, long long allow)
         p->gtp.max_soft = (int32_t)(1.02 * (double)n_v / tp.sps) + 8;
         const bool direct = R % 16 == 0;   // (piece 0 straight into the caller's rows: GardnerSeg::soft_a)
         S.pitch_a = direct ? tp.max_soft : 0;
-        if (hipMalloc((void **)&p->d_gsoft, (size_t)(direct ? K - 1 : K) * R * p->gtp.max_soft * sizeof(float2)) != hipSuccess ||
-            hipMalloc((void **)&p->d_gint, (size_t)4 * K * R * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void **)&p->d_gts, (size_t)2 * K * R * sizeof(float)) != hipSuccess) {
+        DevPtr<float2> gsoft;
+        DevPtr<int32_t> gint;
+        DevPtr<float> gts;
+        if (dev_alloc(gsoft, (size_t)(direct ? K - 1 : K) * R * p->gtp.max_soft * sizeof(float2)) != hipSuccess ||
+            dev_alloc(gint, (size_t)4 * K * R * sizeof(int32_t)) != hipSuccess ||
+            dev_alloc(gts, (size_t)2 * K * R * sizeof(float)) != hipSuccess) {
             (void)hipGetLastError();
-            for (void **q : {(void **)&p->d_gsoft, (void **)&p->d_gint, (void **)&p->d_gts}) {
-                if (*q) (void)hipFree(*q);
-                *q = nullptr;
-            }
             p->gseg = GardnerSeg{};
             return fail(TDM_ERR_NOMEM, "TETRA_GARDNER plan: no memory for the temporaries of " + std::to_string(K) + " pieces per chunk (the plan walks whole chunks)");
         }
-        S.k_in = p->d_gint + (size_t)2 * K * R;
-        S.k_out = p->d_gint + (size_t)3 * K * R;
-        S.t_in = p->d_gts;
-        S.t_out = p->d_gts + (size_t)K * R;
+        S.k_in = gint.get() + (size_t)2 * K * R;
+        S.k_out = gint.get() + (size_t)3 * K * R;
+        S.t_in = gts.get();
+        S.t_out = gts.get() + (size_t)K * R;
+        p->d_gsoft = std::move(gsoft);
+        p->d_gint = std::move(gint);
+        p->d_gts = std::move(gts);
         p->gardner_seg = K;
     }
     return TDM_OK;
-}
-
-static void plan_free(tdm_plan *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    if (p->stream) sync_scratch_release(p->device, p->stream);   // the stream goes away: so does the scratch keyed by it
-    p->cur = nullptr;
-    p->variants.clear();
-    for (auto &kv : p->d_shared)
-        if (kv.second.second) (void)hipFree(kv.second.second);
-    void *ptrs[] = {p->d_work, p->d_gsoft, p->d_gint, p->d_gts, p->d_iq, p->d_pre, p->d_foff, p->d_soft, p->d_margin, p->d_hard, p->d_nsoft, p->d_bp, p->d_tapops, p->d_gy};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
-    if (p->ev_order) (void)hipEventDestroy(p->ev_order);
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    delete p;
 }
 
 extern "C" {
@@ -814,7 +789,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
     if (mode != TDM_MODE_REFERENCE && mode != TDM_MODE_TETRA && mode != TDM_MODE_TETRA_GARDNER) return fail(TDM_ERR_INVALID, "bad mode");
     int rc = use_device(device);
     if (rc) return rc;
-    std::unique_ptr<tdm_plan, void (*)(tdm_plan *)> p(new tdm_plan, plan_free);
+    std::unique_ptr<tdm_plan> p(new tdm_plan);
     p->device = device;
     p->rows = n_carriers;
     p->fmt = in_fmt;
@@ -866,9 +841,9 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
             // the matched filter's constant operands, lane by lane (every carrier of every launch reads the same 4-6 KB)
             std::vector<uint32_t> ops(tetra_tap_operand_words(tp.ntaps));
             tetra_tap_operands(tp.taps, tp.ntaps, ops.data());
-            HIP_TRY(hipMalloc((void **)&p->d_tapops, ops.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpy(p->d_tapops, ops.data(), ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            tp.tap_ops = p->d_tapops;
+            HIP_TRY(dev_alloc(p->d_tapops, ops.size() * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpy(p->d_tapops.get(), ops.data(), ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            tp.tap_ops = p->d_tapops.get();
         }
         {
             std::unique_ptr<Variant> v(new Variant);
@@ -898,9 +873,9 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
             // three launches allocates it (the default fused kernel keeps the filter output in LDS)
             p->gy_pitch = (n_samples + 1) & ~(int64_t)1;
         }
-        HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&p->ev0));
-        HIP_TRY(hipEventCreate(&p->ev1));
+        HIP_TRY(stream_create(p->stream));
+        HIP_TRY(event_create(p->ev0));
+        HIP_TRY(event_create(p->ev1));
         *out = p.release();
         return TDM_OK;
     }
@@ -914,9 +889,9 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
         p->raw_min_blocks = (int64_t)prop.multiProcessorCount * 8;
         if (debug_value("raw_min_blocks") >= 0) p->raw_min_blocks = debug_value("raw_min_blocks");
     }
-    HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&p->ev0));
-    HIP_TRY(hipEventCreate(&p->ev1));
+    HIP_TRY(stream_create(p->stream));
+    HIP_TRY(event_create(p->ev0));
+    HIP_TRY(event_create(p->ev1));
     p->sample_rate = sample_rate;
     if ((rc = plan_select(p.get(), sample_rate, n_samples))) return rc;
     *out = p.release();
@@ -982,7 +957,7 @@ int tdm_gardner_geometry(double sample_rate, int64_t n_samples, int32_t pieces, 
 
 int tdm_plan_destroy(tdm_plan *plan)
 {
-    plan_free(plan);
+    delete plan;
     return TDM_OK;
 }
 
@@ -1026,7 +1001,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
     if (carrier_stride_samples < 0) return fail(TDM_ERR_INVALID, "negative carrier stride");
     HIP_TRY(hipSetDevice(plan->device));
     HipBackend be;
-    be.stream = stream ? (hipStream_t)stream : plan->stream;
+    be.stream = stream ? (hipStream_t)stream : plan->stream.get();
     be.timer = &plan->timer;
     be.device = plan->device;
     if (plan->mode == TDM_MODE_TETRA || plan->mode == TDM_MODE_TETRA_GARDNER) {
@@ -1050,19 +1025,19 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
                 S.ff_first = plan->gardner_ff_first;
                 {
                     HipBackend::Scope s(be, ST_TETRA_LOOP);
-                    fused_done = tetra_gardner_fused_launch(plan->gtp, K * R, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, plan->d_gsoft,
-                                                            plan->d_gint, plan->d_gint + (size_t)K * R, be.stream, &S);
+                    fused_done = tetra_gardner_fused_launch(plan->gtp, K * R, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, plan->d_gsoft.get(),
+                                                            plan->d_gint.get(), plan->d_gint.get() + (size_t)K * R, be.stream, &S);
                 }
                 if (fused_done) {
                     // decisions, with the pieces joined first (pieces 1..: behind piece 0's rows in the temporary unless those
                     // went straight to the caller's rows)
                     HipBackend::Scope s(be, ST_TETRA_DECIDE);
                     if (!S.soft_a)   // (carrier counts that are no multiple of sixteen: piece 0 comes out of the temporary too)
-                        HIP_TRY(hipMemcpy2DAsync(soft, (size_t)tp.max_soft * sizeof(float2), plan->d_gsoft, (size_t)plan->gtp.max_soft * sizeof(float2),
+                        HIP_TRY(hipMemcpy2DAsync(soft, (size_t)tp.max_soft * sizeof(float2), plan->d_gsoft.get(), (size_t)plan->gtp.max_soft * sizeof(float2),
                                                  (size_t)std::min(plan->gtp.max_soft, tp.max_soft) * sizeof(float2), R, hipMemcpyDeviceToDevice, be.stream));
                     tetra_decide_launch(tp, R, (float2 *)soft, n_soft, hard, min_margin, be.stream, &S,
-                                        plan->d_gsoft + (S.soft_a ? 0 : (size_t)R * plan->gtp.max_soft), plan->gtp.max_soft, plan->d_gint,
-                                        plan->d_gint + (size_t)K * R, best_phase);
+                                        plan->d_gsoft.get() + (S.soft_a ? 0 : (size_t)R * plan->gtp.max_soft), plan->gtp.max_soft, plan->d_gint.get(),
+                                        plan->d_gint.get() + (size_t)K * R, best_phase);
                     if (be.err != hipSuccess) return fail(TDM_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(be.err));
                     return TDM_OK;
                 }
@@ -1077,15 +1052,15 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
                 return fail(TDM_ERR_UNSUPPORTED, "gardner_ff_start needs the fused Gardner kernel (gardner_fused switched off, or no kernel for this tap count / batch)");
             const bool three = !fused_done;   // (gardner_fused = 0, no fused kernel for this tap count, or too many carriers for it)
             if (three && !plan->d_gy)
-                HIP_TRY(hipMalloc((void **)&plan->d_gy, (size_t)plan->rows * plan->gy_pitch * sizeof(float2)));
+                HIP_TRY(dev_alloc(plan->d_gy, (size_t)plan->rows * plan->gy_pitch * sizeof(float2)));
             if (three && (stages & 1)) {
                 HipBackend::Scope s(be, ST_TETRA_MF);
-                if (!tetra_mf_launch(tp, plan->rows, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, plan->d_gy, plan->gy_pitch, be.stream))
+                if (!tetra_mf_launch(tp, plan->rows, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, plan->d_gy.get(), plan->gy_pitch, be.stream))
                     return fail(TDM_ERR_UNSUPPORTED, "no RRC kernel instantiated for this tap count");
             }
             if (three && (stages & 2)) {
                 HipBackend::Scope s(be, ST_TETRA_LOOP);
-                tetra_gardner_loop_launch(tp, plan->rows, plan->d_gy, plan->gy_pitch, (float2 *)soft, n_soft, best_phase, be.stream);
+                tetra_gardner_loop_launch(tp, plan->rows, plan->d_gy.get(), plan->gy_pitch, (float2 *)soft, n_soft, best_phase, be.stream);
             }
             if (stages & 4) {
                 HipBackend::Scope s(be, ST_TETRA_DECIDE);
@@ -1145,7 +1120,7 @@ int tdm_plan_rrc_filter(tdm_plan *plan, const void *iq, int64_t carrier_stride_s
     if (carrier_stride_samples < plan->tp.n || y_pitch < plan->tp.n || (y_pitch & 1)) return fail(TDM_ERR_INVALID, "stride / pitch (even, >= chunk length)");
     HIP_TRY(hipSetDevice(plan->device));
     HipBackend be;
-    be.stream = stream ? (hipStream_t)stream : plan->stream;
+    be.stream = stream ? (hipStream_t)stream : plan->stream.get();
     be.timer = &plan->timer;
     {
         HipBackend::Scope s(be, ST_TETRA_MF);
@@ -1165,7 +1140,7 @@ int tdm_set_stream(void *stream)
 int tdm_plan_stream(tdm_plan *plan, void **stream)
 {
     if (!plan || !stream) return fail(TDM_ERR_INVALID, "null argument");
-    *stream = (void *)plan->stream;
+    *stream = (void *)plan->stream.get();
     return TDM_OK;
 }
 
@@ -1175,9 +1150,9 @@ int tdm_plan_wait_for(tdm_plan *plan, tdm_plan *other)
     if (plan == other) return TDM_OK;
     if (plan->device != other->device) return fail(TDM_ERR_UNSUPPORTED, "tdm_plan_wait_for: the two plans are on different devices");
     HIP_TRY(hipSetDevice(plan->device));
-    if (!other->ev_order) HIP_TRY(hipEventCreateWithFlags(&other->ev_order, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(other->ev_order, other->stream));
-    HIP_TRY(hipStreamWaitEvent(plan->stream, other->ev_order, 0));
+    if (!other->ev_order) HIP_TRY(event_create(other->ev_order, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(other->ev_order.get(), other->stream.get()));
+    HIP_TRY(hipStreamWaitEvent(plan->stream.get(), other->ev_order.get(), 0));
     return TDM_OK;
 }
 
@@ -1185,7 +1160,7 @@ int tdm_plan_sync(tdm_plan *plan)
 {
     if (!plan) return fail(TDM_ERR_INVALID, "null plan");
     HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipStreamSynchronize(plan->stream));
+    HIP_TRY(hipStreamSynchronize(plan->stream.get()));
     return TDM_OK;
 }
 
@@ -1205,43 +1180,38 @@ int tdm_process(tdm_plan *plan, const void *iq, int64_t carrier_stride_samples, 
                                                     : (size_t)(in_rows - 1) * carrier_stride_samples + h.n;
     const size_t bytes = span * fmt_bytes(plan->fmt);
     if (plan->d_iq_bytes < bytes) {
-        if (plan->d_iq) (void)hipFree(plan->d_iq);
-        plan->d_iq = nullptr;
         plan->d_iq_bytes = 0;
-        HIP_TRY(hipMalloc(&plan->d_iq, bytes));
+        HIP_TRY(dev_alloc(plan->d_iq, bytes));
         plan->d_iq_bytes = bytes;
     }
     if (plan->staging_ready && plan->staging_soft < (size_t)rows * h.max_soft) plan->staging_ready = false;   // a longer chunk than the buffers were made for
     if (!plan->staging_ready) {
-        // all or nothing: a failed allocation leaves the flag clear, the next call starts over (plan_free releases
-        // whatever a failed attempt left behind)
-        void **slots[] = {(void **)&plan->d_pre, (void **)&plan->d_foff, (void **)&plan->d_soft, (void **)&plan->d_hard,
-                          (void **)&plan->d_nsoft, (void **)&plan->d_bp, (void **)&plan->d_margin};
-        const size_t sizes[] = {rows * sizeof(double), rows * sizeof(double),
-                                (size_t)rows * h.max_soft * 2 * sizeof(double),   // cf32 in TETRA mode uses half
-                                (size_t)rows * h.max_soft, rows * sizeof(int32_t), rows * sizeof(int32_t), rows * sizeof(double)};
-        for (int i = 0; i < 7; ++i) {
-            if (*slots[i]) { (void)hipFree(*slots[i]); *slots[i] = nullptr; }
-            HIP_TRY(hipMalloc(slots[i], sizes[i]));
-        }
+        // all or nothing: a failed allocation leaves the flag clear, the next call starts over
+        HIP_TRY(dev_alloc(plan->d_pre, rows * sizeof(double)));
+        HIP_TRY(dev_alloc(plan->d_foff, rows * sizeof(double)));
+        HIP_TRY(dev_alloc(plan->d_soft, (size_t)rows * h.max_soft * 2 * sizeof(double)));   // (cf32 in TETRA mode uses half)
+        HIP_TRY(dev_alloc(plan->d_hard, (size_t)rows * h.max_soft));
+        HIP_TRY(dev_alloc(plan->d_nsoft, rows * sizeof(int32_t)));
+        HIP_TRY(dev_alloc(plan->d_bp, rows * sizeof(int32_t)));
+        HIP_TRY(dev_alloc(plan->d_margin, rows * sizeof(double)));
         plan->staging_ready = true;
         plan->staging_soft = (size_t)rows * h.max_soft;
     }
-    hipStream_t st = plan->stream;
-    HIP_TRY(hipMemcpyAsync(plan->d_iq, iq, bytes, hipMemcpyHostToDevice, st));
-    if (pre_shift_hz) HIP_TRY(hipMemcpyAsync(plan->d_pre, pre_shift_hz, rows * sizeof(double), hipMemcpyHostToDevice, st));
-    if (freq_offset_hz) HIP_TRY(hipMemcpyAsync(plan->d_foff, freq_offset_hz, rows * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(plan->d_hard, 0, (size_t)rows * h.max_soft, st));
-    int rc = tdm_process_device(plan, plan->d_iq, carrier_stride_samples, pre_shift_hz ? plan->d_pre : nullptr,
-                                freq_offset_hz ? plan->d_foff : nullptr, plan->d_hard, plan->d_soft, plan->d_nsoft,
-                                plan->d_bp, plan->d_margin, nullptr);
+    hipStream_t st = plan->stream.get();
+    HIP_TRY(hipMemcpyAsync(plan->d_iq.get(), iq, bytes, hipMemcpyHostToDevice, st));
+    if (pre_shift_hz) HIP_TRY(hipMemcpyAsync(plan->d_pre.get(), pre_shift_hz, rows * sizeof(double), hipMemcpyHostToDevice, st));
+    if (freq_offset_hz) HIP_TRY(hipMemcpyAsync(plan->d_foff.get(), freq_offset_hz, rows * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(plan->d_hard.get(), 0, (size_t)rows * h.max_soft, st));
+    int rc = tdm_process_device(plan, plan->d_iq.get(), carrier_stride_samples, pre_shift_hz ? plan->d_pre.get() : nullptr,
+                                freq_offset_hz ? plan->d_foff.get() : nullptr, plan->d_hard.get(), plan->d_soft.get(), plan->d_nsoft.get(),
+                                plan->d_bp.get(), plan->d_margin.get(), nullptr);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(hard, plan->d_hard, (size_t)rows * h.max_soft, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hard, plan->d_hard.get(), (size_t)rows * h.max_soft, hipMemcpyDeviceToHost, st));
     const size_t soft_elem = plan->mode != TDM_MODE_REFERENCE ? 2 * sizeof(float) : 2 * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(soft, plan->d_soft, (size_t)rows * h.max_soft * soft_elem, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(n_soft, plan->d_nsoft, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (best_phase) HIP_TRY(hipMemcpyAsync(best_phase, plan->d_bp, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (min_margin) HIP_TRY(hipMemcpyAsync(min_margin, plan->d_margin, rows * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(soft, plan->d_soft.get(), (size_t)rows * h.max_soft * soft_elem, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(n_soft, plan->d_nsoft.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (best_phase) HIP_TRY(hipMemcpyAsync(best_phase, plan->d_bp.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (min_margin) HIP_TRY(hipMemcpyAsync(min_margin, plan->d_margin.get(), rows * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return TDM_OK;
 }
@@ -1262,99 +1232,72 @@ int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, con
     const size_t in_bytes = (size_t)rows * h.n * fmt_bytes(plan->fmt);
     const size_t soft_elem = plan->mode != TDM_MODE_REFERENCE ? 2 * sizeof(float) : 2 * sizeof(double);
     const size_t hard_bytes = (size_t)rows * h.max_soft, soft_bytes = (size_t)rows * h.max_soft * soft_elem;
-    // pin the caller's buffers in place so the copies are truly asynchronous (best effort).  A buffer that is page-locked
-    // already (tdm_host_register, hipHostMalloc) is left alone: the runtime accepts a second hipHostRegister of a
-    // registered range, and the hipHostUnregister at the end would then drop the caller's own registration.
-    // (hipHostGetFlags does not see a hipHostRegister'ed range; the pointer's attributes do: type host, also inside it)
-    auto pin = [](const void *p, size_t bytes) {
-        void *q = const_cast<void *>(p);
-        hipPointerAttribute_t a{};
-        if (hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeHost) return false;
-        return hipHostRegister(q, bytes, hipHostRegisterDefault) == hipSuccess;
-    };
-    const bool pin_in = pin(iq, in_bytes * n_batches);
-    const bool pin_h = pin(hard, hard_bytes * n_batches);
-    const bool pin_s = pin(soft, soft_bytes * n_batches);
-    (void)hipGetLastError();
+    // pin the caller's buffers in place so the copies are truly asynchronous (best effort; host_pin leaves a buffer that is
+    // page-locked already alone)
+    const HostPin pin_in = host_pin(iq, in_bytes * n_batches), pin_h = host_pin(hard, hard_bytes * n_batches),
+                  pin_s = host_pin(soft, soft_bytes * n_batches);
     struct Slot {
-        void *iq = nullptr; uint8_t *hard = nullptr; void *soft = nullptr; int32_t *ns = nullptr, *bp = nullptr; double *mm = nullptr;
-        hipEvent_t in_done{}, comp_done{}, out_done{};
+        DevPtr<void> iq, soft; DevPtr<uint8_t> hard; DevPtr<int32_t> ns, bp; DevPtr<double> mm;
+        Event in_done, comp_done, out_done;
     } sl[2];
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    double *d_fo = nullptr;
-    int rc = TDM_OK;
-    auto cleanup = [&]() {
-        // copies and kernels may still be in flight on the error path: drain before buffers and pins go away
-        if (s_in) (void)hipStreamSynchronize(s_in);
-        if (s_out) (void)hipStreamSynchronize(s_out);
-        (void)hipStreamSynchronize(plan->stream);
-        for (auto &x : sl) {
-            void *ps[] = {x.iq, x.hard, x.soft, x.ns, x.bp, x.mm};
-            for (void *q : ps) if (q) (void)hipFree(q);
-            if (x.in_done) (void)hipEventDestroy(x.in_done);
-            if (x.comp_done) (void)hipEventDestroy(x.comp_done);
-            if (x.out_done) (void)hipEventDestroy(x.out_done);
+    Stream s_in, s_out;
+    DevPtr<double> d_fo;
+    // copies and kernels may still be in flight on an error path: this guard, destroyed first, drains them on every exit
+    // before the buffers and pins above go away
+    struct Drain {
+        const Stream &in, &out;
+        hipStream_t plan;
+        ~Drain()
+        {
+            if (in) (void)hipStreamSynchronize(in.get());
+            if (out) (void)hipStreamSynchronize(out.get());
+            (void)hipStreamSynchronize(plan);
+            (void)hipGetLastError();
         }
-        if (d_fo) (void)hipFree(d_fo);
-        if (s_in) (void)hipStreamDestroy(s_in);
-        if (s_out) (void)hipStreamDestroy(s_out);
-        if (pin_in) (void)hipHostUnregister((void *)iq);
-        if (pin_h) (void)hipHostUnregister(hard);
-        if (pin_s) (void)hipHostUnregister(soft);
-    };
-#define PIPE_TRY(expr)                                                                     \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (void)hipGetLastError();                                                       \
-            rc = fail(TDM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-            cleanup();                                                                     \
-            return rc;                                                                     \
-        }                                                                                  \
-    } while (0)
-    PIPE_TRY(hipStreamCreateWithFlags(&s_in, hipStreamNonBlocking));
-    PIPE_TRY(hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking));
+    } drain{s_in, s_out, plan->stream.get()};
+    HIP_TRY(stream_create(s_in));
+    HIP_TRY(stream_create(s_out));
     for (auto &x : sl) {
-        PIPE_TRY(hipMalloc(&x.iq, in_bytes));
-        PIPE_TRY(hipMalloc(&x.hard, hard_bytes));
-        PIPE_TRY(hipMalloc(&x.soft, soft_bytes));
-        PIPE_TRY(hipMalloc(&x.ns, rows * sizeof(int32_t)));
-        PIPE_TRY(hipMalloc(&x.bp, rows * sizeof(int32_t)));
-        PIPE_TRY(hipMalloc(&x.mm, rows * sizeof(double)));
-        PIPE_TRY(hipEventCreateWithFlags(&x.in_done, hipEventDisableTiming));
-        PIPE_TRY(hipEventCreateWithFlags(&x.comp_done, hipEventDisableTiming));
-        PIPE_TRY(hipEventCreateWithFlags(&x.out_done, hipEventDisableTiming));
+        HIP_TRY(dev_alloc(x.iq, in_bytes));
+        HIP_TRY(dev_alloc(x.hard, hard_bytes));
+        HIP_TRY(dev_alloc(x.soft, soft_bytes));
+        HIP_TRY(dev_alloc(x.ns, rows * sizeof(int32_t)));
+        HIP_TRY(dev_alloc(x.bp, rows * sizeof(int32_t)));
+        HIP_TRY(dev_alloc(x.mm, rows * sizeof(double)));
+        HIP_TRY(event_create(x.in_done, hipEventDisableTiming));
+        HIP_TRY(event_create(x.comp_done, hipEventDisableTiming));
+        HIP_TRY(event_create(x.out_done, hipEventDisableTiming));
     }
     if (freq_offset_hz) {
-        PIPE_TRY(hipMalloc(&d_fo, rows * sizeof(double)));
-        PIPE_TRY(hipMemcpy(d_fo, freq_offset_hz, rows * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(d_fo, rows * sizeof(double)));
+        HIP_TRY(hipMemcpy(d_fo.get(), freq_offset_hz, rows * sizeof(double), hipMemcpyHostToDevice));
     }
     const char *src = (const char *)iq;
+    hipStream_t st = plan->stream.get();
     for (int64_t b = 0; b < n_batches; ++b) {
         Slot &x = sl[b & 1];
         if (b >= 2) {
-            PIPE_TRY(hipStreamWaitEvent(s_in, x.comp_done, 0));        // slot's input consumed
-            PIPE_TRY(hipStreamWaitEvent(plan->stream, x.out_done, 0)); // slot's outputs copied out
+            HIP_TRY(hipStreamWaitEvent(s_in.get(), x.comp_done.get(), 0));   // slot's input consumed
+            HIP_TRY(hipStreamWaitEvent(st, x.out_done.get(), 0));            // slot's outputs copied out
         }
-        PIPE_TRY(hipMemcpyAsync(x.iq, src + (size_t)b * in_bytes, in_bytes, hipMemcpyHostToDevice, s_in));
-        PIPE_TRY(hipEventRecord(x.in_done, s_in));
-        PIPE_TRY(hipStreamWaitEvent(plan->stream, x.in_done, 0));
-        PIPE_TRY(hipMemsetAsync(x.hard, 0, hard_bytes, plan->stream));
-        rc = tdm_process_device(plan, x.iq, h.n, nullptr, d_fo, x.hard, (double *)x.soft, x.ns, x.bp, x.mm, nullptr);
-        if (rc) { cleanup(); return rc; }
-        PIPE_TRY(hipEventRecord(x.comp_done, plan->stream));
-        PIPE_TRY(hipStreamWaitEvent(s_out, x.comp_done, 0));
-        PIPE_TRY(hipMemcpyAsync(hard + (size_t)b * hard_bytes, x.hard, hard_bytes, hipMemcpyDeviceToHost, s_out));
-        PIPE_TRY(hipMemcpyAsync((char *)soft + (size_t)b * soft_bytes, x.soft, soft_bytes, hipMemcpyDeviceToHost, s_out));
-        PIPE_TRY(hipMemcpyAsync(n_soft + (size_t)b * rows, x.ns, rows * sizeof(int32_t), hipMemcpyDeviceToHost, s_out));
-        if (best_phase) PIPE_TRY(hipMemcpyAsync(best_phase + (size_t)b * rows, x.bp, rows * sizeof(int32_t), hipMemcpyDeviceToHost, s_out));
-        if (min_margin) PIPE_TRY(hipMemcpyAsync(min_margin + (size_t)b * rows, x.mm, rows * sizeof(double), hipMemcpyDeviceToHost, s_out));
-        PIPE_TRY(hipEventRecord(x.out_done, s_out));
+        HIP_TRY(hipMemcpyAsync(x.iq.get(), src + (size_t)b * in_bytes, in_bytes, hipMemcpyHostToDevice, s_in.get()));
+        HIP_TRY(hipEventRecord(x.in_done.get(), s_in.get()));
+        HIP_TRY(hipStreamWaitEvent(st, x.in_done.get(), 0));
+        HIP_TRY(hipMemsetAsync(x.hard.get(), 0, hard_bytes, st));
+        const int rc = tdm_process_device(plan, x.iq.get(), h.n, nullptr, d_fo.get(), x.hard.get(), (double *)x.soft.get(), x.ns.get(),
+                                          x.bp.get(), x.mm.get(), nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(x.comp_done.get(), st));
+        HIP_TRY(hipStreamWaitEvent(s_out.get(), x.comp_done.get(), 0));
+        HIP_TRY(hipMemcpyAsync(hard + (size_t)b * hard_bytes, x.hard.get(), hard_bytes, hipMemcpyDeviceToHost, s_out.get()));
+        HIP_TRY(hipMemcpyAsync((char *)soft + (size_t)b * soft_bytes, x.soft.get(), soft_bytes, hipMemcpyDeviceToHost, s_out.get()));
+        HIP_TRY(hipMemcpyAsync(n_soft + (size_t)b * rows, x.ns.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost, s_out.get()));
+        if (best_phase) HIP_TRY(hipMemcpyAsync(best_phase + (size_t)b * rows, x.bp.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost, s_out.get()));
+        if (min_margin) HIP_TRY(hipMemcpyAsync(min_margin + (size_t)b * rows, x.mm.get(), rows * sizeof(double), hipMemcpyDeviceToHost, s_out.get()));
+        HIP_TRY(hipEventRecord(x.out_done.get(), s_out.get()));
     }
-    PIPE_TRY(hipStreamSynchronize(s_out));
-    PIPE_TRY(hipStreamSynchronize(plan->stream));
-#undef PIPE_TRY
-    cleanup();
+    HIP_TRY(hipStreamSynchronize(s_out.get()));
+    HIP_TRY(hipStreamSynchronize(st));
     return TDM_OK;
 }
 
@@ -1363,14 +1306,17 @@ int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, con
 // slot's previous step (ev_done) -> H2D -> ev_in; plan stream waits ev_in -> kernels -> D2H of the outputs -> ev_done.
 // The host side (stream_ring.hpp) hands a slot out again only after its result was collected, i.e. after ev_done.
 struct StreamSlot {
-    tdm_plan *plan = nullptr;
+    std::unique_ptr<tdm_plan> plan;
     hipStream_t st = nullptr;                // the plan's own stream
-    void *d_iq = nullptr, *h_iq = nullptr;
-    uint8_t *d_hard = nullptr, *h_hard = nullptr;
-    void *d_soft = nullptr, *h_soft = nullptr;
-    int32_t *d_ns = nullptr, *h_ns = nullptr, *d_bp = nullptr, *h_bp = nullptr;
-    double *d_mm = nullptr, *h_mm = nullptr;
-    hipEvent_t ev_in = nullptr, ev_done = nullptr;
+    DevPtr<void> d_iq, d_soft;
+    HostPtr<void> h_iq, h_soft;
+    DevPtr<uint8_t> d_hard;
+    HostPtr<uint8_t> h_hard;
+    DevPtr<int32_t> d_ns, d_bp;
+    HostPtr<int32_t> h_ns, h_bp;
+    DevPtr<double> d_mm;
+    HostPtr<double> h_mm;
+    Event ev_in, ev_done;
     int64_t n_samples = 0;                   // of the step in the slot
     int32_t n_valid_rows = 0, max_soft = 0;
 };
@@ -1380,34 +1326,18 @@ struct tdm_stream {
     int64_t chunk = 0;
     int32_t max_soft = 0;                    // at the full chunk: the outputs' capacity per row
     size_t soft_elem = 0;
-    double *d_foff = nullptr, *d_pre = nullptr;   // per plan row, read by every slot's plan
-    hipStream_t s_h2d = nullptr;
+    DevPtr<double> d_foff, d_pre;            // per plan row, read by every slot's plan
+    Stream s_h2d;
     std::vector<StreamSlot> slots;
     StreamRing ring;
-};
-
-static void stream_free(tdm_stream *s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->s_h2d) (void)hipStreamSynchronize(s->s_h2d);
-    for (auto &x : s->slots)
-        if (x.st) (void)hipStreamSynchronize(x.st);
-    for (auto &x : s->slots) {
-        void *dev[] = {x.d_iq, x.d_hard, x.d_soft, x.d_ns, x.d_bp, x.d_mm};
-        for (void *q : dev) if (q) (void)hipFree(q);
-        void *host[] = {x.h_iq, x.h_hard, x.h_soft, x.h_ns, x.h_bp, x.h_mm};
-        for (void *q : host) if (q) (void)hipHostFree(q);
-        if (x.ev_in) (void)hipEventDestroy(x.ev_in);
-        if (x.ev_done) (void)hipEventDestroy(x.ev_done);
-        if (x.plan) tdm_plan_destroy(x.plan);
+    ~tdm_stream()   // steps may still be in flight: drained before the members go
+    {
+        (void)hipSetDevice(device);
+        if (s_h2d) (void)hipStreamSynchronize(s_h2d.get());
+        for (auto &x : slots)
+            if (x.st) (void)hipStreamSynchronize(x.st);
     }
-    if (s->d_foff) (void)hipFree(s->d_foff);
-    if (s->d_pre) (void)hipFree(s->d_pre);
-    if (s->s_h2d) (void)hipStreamDestroy(s->s_h2d);
-    (void)hipGetLastError();
-    delete s;
-}
+};
 
 int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int32_t in_fmt, int32_t mode, int32_t depth,
                       int32_t flags, const double *freq_offset_hz, const double *pre_shift_hz, int32_t rows_per_chunk,
@@ -1429,7 +1359,7 @@ int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int
         return fail(TDM_ERR_UNSUPPORTED, "tdm_stream_create: pre_shift_hz, freq_offset_hz and rows_per_chunk > 1 are reference-mode inputs");
     int rc = use_device(device);
     if (rc) return rc;
-    std::unique_ptr<tdm_stream, void (*)(tdm_stream *)> s(new tdm_stream, stream_free);
+    std::unique_ptr<tdm_stream> s(new tdm_stream);
     s->device = device;
     s->rows = n_rows;
     s->rpc = rows_per_chunk;
@@ -1442,42 +1372,44 @@ int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int
     s->ring = StreamRing(depth);
     s->slots.resize((size_t)depth);
     for (auto &x : s->slots) {
-        if ((rc = tdm_plan_create(sample_rate, n_samples, n_rows, in_fmt, mode, device, &x.plan))) return rc;
-        if (rows_per_chunk > 1 && (rc = tdm_plan_option(x.plan, "rows_per_chunk", rows_per_chunk))) return rc;
-        x.st = x.plan->stream;
+        tdm_plan *plan = nullptr;
+        if ((rc = tdm_plan_create(sample_rate, n_samples, n_rows, in_fmt, mode, device, &plan))) return rc;
+        x.plan.reset(plan);
+        if (rows_per_chunk > 1 && (rc = tdm_plan_option(plan, "rows_per_chunk", rows_per_chunk))) return rc;
+        x.st = plan->stream.get();
     }
     s->max_soft = (int32_t)s->slots[0].plan->h().max_soft;
     const size_t in_bytes = (size_t)s->in_rows * n_samples * fmt_bytes(in_fmt);
     const size_t hard_bytes = (size_t)n_rows * s->max_soft, soft_bytes = hard_bytes * s->soft_elem;
     const unsigned in_flags = debug_value("stream_wc") == 1 ? hipHostMallocWriteCombined : hipHostMallocDefault;
     for (auto &x : s->slots) {
-        HIP_TRY(hipMalloc(&x.d_iq, in_bytes));
-        HIP_TRY(hipMemset(x.d_iq, 0, in_bytes));
-        HIP_TRY(hipHostMalloc(&x.h_iq, in_bytes, in_flags));
-        std::memset(x.h_iq, 0, in_bytes);
-        HIP_TRY(hipMalloc((void **)&x.d_hard, hard_bytes));
-        HIP_TRY(hipHostMalloc((void **)&x.h_hard, hard_bytes, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&x.d_soft, soft_bytes));
-        if (flags & TDM_STREAM_SOFT) HIP_TRY(hipHostMalloc(&x.h_soft, soft_bytes, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&x.d_ns, n_rows * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&x.d_bp, n_rows * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&x.d_mm, n_rows * sizeof(double)));
-        HIP_TRY(hipHostMalloc((void **)&x.h_ns, n_rows * sizeof(int32_t), hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void **)&x.h_bp, n_rows * sizeof(int32_t), hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void **)&x.h_mm, n_rows * sizeof(double), hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&x.ev_in, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&x.ev_done, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(x.ev_done, x.st));   // (the first step's copy then waits for nothing)
+        HIP_TRY(dev_alloc(x.d_iq, in_bytes));
+        HIP_TRY(hipMemset(x.d_iq.get(), 0, in_bytes));
+        HIP_TRY(host_alloc(x.h_iq, in_bytes, in_flags));
+        std::memset(x.h_iq.get(), 0, in_bytes);
+        HIP_TRY(dev_alloc(x.d_hard, hard_bytes));
+        HIP_TRY(host_alloc(x.h_hard, hard_bytes));
+        HIP_TRY(dev_alloc(x.d_soft, soft_bytes));
+        if (flags & TDM_STREAM_SOFT) HIP_TRY(host_alloc(x.h_soft, soft_bytes));
+        HIP_TRY(dev_alloc(x.d_ns, n_rows * sizeof(int32_t)));
+        HIP_TRY(dev_alloc(x.d_bp, n_rows * sizeof(int32_t)));
+        HIP_TRY(dev_alloc(x.d_mm, n_rows * sizeof(double)));
+        HIP_TRY(host_alloc(x.h_ns, n_rows * sizeof(int32_t)));
+        HIP_TRY(host_alloc(x.h_bp, n_rows * sizeof(int32_t)));
+        HIP_TRY(host_alloc(x.h_mm, n_rows * sizeof(double)));
+        HIP_TRY(event_create(x.ev_in, hipEventDisableTiming));
+        HIP_TRY(event_create(x.ev_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(x.ev_done.get(), x.st));   // (the first step's copy then waits for nothing)
     }
     if (freq_offset_hz) {
-        HIP_TRY(hipMalloc((void **)&s->d_foff, n_rows * sizeof(double)));
-        HIP_TRY(hipMemcpy(s->d_foff, freq_offset_hz, n_rows * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(s->d_foff, n_rows * sizeof(double)));
+        HIP_TRY(hipMemcpy(s->d_foff.get(), freq_offset_hz, n_rows * sizeof(double), hipMemcpyHostToDevice));
     }
     if (pre_shift_hz) {
-        HIP_TRY(hipMalloc((void **)&s->d_pre, n_rows * sizeof(double)));
-        HIP_TRY(hipMemcpy(s->d_pre, pre_shift_hz, n_rows * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(s->d_pre, n_rows * sizeof(double)));
+        HIP_TRY(hipMemcpy(s->d_pre.get(), pre_shift_hz, n_rows * sizeof(double), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipStreamCreateWithFlags(&s->s_h2d, hipStreamNonBlocking));
+    HIP_TRY(stream_create(s->s_h2d));
     HIP_TRY(hipStreamSynchronize(nullptr));   // (create only: the zeroing above is done before the first step's copy)
     *out = s.release();
     return TDM_OK;
@@ -1485,7 +1417,7 @@ int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int
 
 int tdm_stream_destroy(tdm_stream *s)
 {
-    stream_free(s);
+    delete s;
     return TDM_OK;
 }
 
@@ -1499,9 +1431,36 @@ int tdm_stream_acquire(tdm_stream *s, void **iq, int64_t *seq)
     // (collected means waited for: ev_done has completed and nothing reads this input any more; the wait below costs
     //  nothing then and keeps the rule even after a submit that failed half-way)
     HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipEventSynchronize(s->slots[(size_t)k].ev_done));
-    *iq = s->slots[(size_t)k].h_iq;
+    HIP_TRY(hipEventSynchronize(s->slots[(size_t)k].ev_done.get()));
+    *iq = s->slots[(size_t)k].h_iq.get();
     if (seq) *seq = q;
+    return TDM_OK;
+}
+
+// the enqueue of one step on slot x (tdm_stream_submit; it drains the slot when this fails part of the way)
+static int stream_enqueue(tdm_stream *s, StreamSlot &x, int64_t n_samples, int32_t n_valid_inputs, int32_t valid_rows, int32_t ms)
+{
+    const size_t bytes = (size_t)n_valid_inputs * n_samples * fmt_bytes(s->fmt), hard_bytes = (size_t)s->rows * ms;
+    HIP_TRY(hipStreamWaitEvent(s->s_h2d.get(), x.ev_done.get(), 0));   // the slot's previous step no longer reads its device input
+    HIP_TRY(hipMemcpyAsync(x.d_iq.get(), x.h_iq.get(), bytes, hipMemcpyHostToDevice, s->s_h2d.get()));
+    HIP_TRY(hipEventRecord(x.ev_in.get(), s->s_h2d.get()));
+    HIP_TRY(hipStreamWaitEvent(x.st, x.ev_in.get(), 0));
+    HIP_TRY(hipMemsetAsync(x.d_hard.get(), 0, hard_bytes, x.st));   // (as tdm_process: hard beyond n_hard is 0)
+    const int rc = tdm_process_device(x.plan.get(), x.d_iq.get(), n_samples, s->d_pre.get(), s->d_foff.get(), x.d_hard.get(),
+                                      (double *)x.d_soft.get(), x.d_ns.get(), x.d_bp.get(), x.d_mm.get(), nullptr);
+    if (rc) return rc;
+    if (valid_rows < s->rows) {
+        const size_t rest = (size_t)(s->rows - valid_rows);
+        HIP_TRY(hipMemsetAsync(x.d_ns.get() + valid_rows, 0, rest * sizeof(int32_t), x.st));
+        HIP_TRY(hipMemsetAsync(x.d_bp.get() + valid_rows, 0, rest * sizeof(int32_t), x.st));
+        HIP_TRY(hipMemsetAsync(x.d_mm.get() + valid_rows, 0, rest * sizeof(double), x.st));
+    }
+    HIP_TRY(hipMemcpyAsync(x.h_hard.get(), x.d_hard.get(), hard_bytes, hipMemcpyDeviceToHost, x.st));
+    if (x.h_soft) HIP_TRY(hipMemcpyAsync(x.h_soft.get(), x.d_soft.get(), hard_bytes * s->soft_elem, hipMemcpyDeviceToHost, x.st));
+    HIP_TRY(hipMemcpyAsync(x.h_ns.get(), x.d_ns.get(), s->rows * sizeof(int32_t), hipMemcpyDeviceToHost, x.st));
+    HIP_TRY(hipMemcpyAsync(x.h_bp.get(), x.d_bp.get(), s->rows * sizeof(int32_t), hipMemcpyDeviceToHost, x.st));
+    HIP_TRY(hipMemcpyAsync(x.h_mm.get(), x.d_mm.get(), s->rows * sizeof(double), hipMemcpyDeviceToHost, x.st));
+    HIP_TRY(hipEventRecord(x.ev_done.get(), x.st));
     return TDM_OK;
 }
 
@@ -1518,55 +1477,22 @@ int tdm_stream_submit(tdm_stream *s, int64_t n_samples, int32_t n_valid_inputs)
     StreamSlot &x = s->slots[(size_t)k];
     HIP_TRY(hipSetDevice(s->device));
     // (reference mode: a no-op at the plan's length; the plan is idle, its last step was collected.  TETRA modes: full reads only)
-    int rc = s->mode == TDM_MODE_REFERENCE ? tdm_plan_resize(x.plan, n_samples) : TDM_OK;
+    int rc = s->mode == TDM_MODE_REFERENCE ? tdm_plan_resize(x.plan.get(), n_samples) : TDM_OK;
     if (rc) return rc;
     const int32_t ms = (int32_t)x.plan->h().max_soft;
     if (ms > s->max_soft) {
-        (void)tdm_plan_resize(x.plan, s->chunk);
+        (void)tdm_plan_resize(x.plan.get(), s->chunk);
         return fail(TDM_ERR_UNSUPPORTED, "tdm_stream_submit: this read length needs more symbol room per row than the chunk's");
     }
     const int32_t valid_rows = n_valid_inputs * s->rpc;
-    const size_t bytes = (size_t)n_valid_inputs * n_samples * fmt_bytes(s->fmt), hard_bytes = (size_t)s->rows * ms;
-    // on a failure after something was enqueued: wait for it, so that the slot's buffers are idle again (the ring is unchanged
-    // and the slot stays acquired)
-#define STREAM_TRY(expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (void)hipGetLastError();                                                       \
-            rc = fail(TDM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-            (void)hipStreamSynchronize(s->s_h2d);                                          \
-            (void)hipStreamSynchronize(x.st);                                              \
-            (void)hipGetLastError();                                                       \
-            return rc;                                                                     \
-        }                                                                                  \
-    } while (0)
-    STREAM_TRY(hipStreamWaitEvent(s->s_h2d, x.ev_done, 0));   // the slot's previous step no longer reads its device input
-    STREAM_TRY(hipMemcpyAsync(x.d_iq, x.h_iq, bytes, hipMemcpyHostToDevice, s->s_h2d));
-    STREAM_TRY(hipEventRecord(x.ev_in, s->s_h2d));
-    STREAM_TRY(hipStreamWaitEvent(x.st, x.ev_in, 0));
-    STREAM_TRY(hipMemsetAsync(x.d_hard, 0, hard_bytes, x.st));   // (as tdm_process: hard beyond n_hard is 0)
-    rc = tdm_process_device(x.plan, x.d_iq, n_samples, s->d_pre, s->d_foff, x.d_hard, (double *)x.d_soft, x.d_ns, x.d_bp,
-                            x.d_mm, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(s->s_h2d);
+    if ((rc = stream_enqueue(s, x, n_samples, n_valid_inputs, valid_rows, ms))) {
+        // something may have been enqueued: wait for it, so that the slot's buffers are idle again (the ring is unchanged
+        // and the slot stays acquired)
+        (void)hipStreamSynchronize(s->s_h2d.get());
         (void)hipStreamSynchronize(x.st);
         (void)hipGetLastError();
         return rc;
     }
-    if (valid_rows < s->rows) {
-        const size_t rest = (size_t)(s->rows - valid_rows);
-        STREAM_TRY(hipMemsetAsync(x.d_ns + valid_rows, 0, rest * sizeof(int32_t), x.st));
-        STREAM_TRY(hipMemsetAsync(x.d_bp + valid_rows, 0, rest * sizeof(int32_t), x.st));
-        STREAM_TRY(hipMemsetAsync(x.d_mm + valid_rows, 0, rest * sizeof(double), x.st));
-    }
-    STREAM_TRY(hipMemcpyAsync(x.h_hard, x.d_hard, hard_bytes, hipMemcpyDeviceToHost, x.st));
-    if (x.h_soft) STREAM_TRY(hipMemcpyAsync(x.h_soft, x.d_soft, hard_bytes * s->soft_elem, hipMemcpyDeviceToHost, x.st));
-    STREAM_TRY(hipMemcpyAsync(x.h_ns, x.d_ns, s->rows * sizeof(int32_t), hipMemcpyDeviceToHost, x.st));
-    STREAM_TRY(hipMemcpyAsync(x.h_bp, x.d_bp, s->rows * sizeof(int32_t), hipMemcpyDeviceToHost, x.st));
-    STREAM_TRY(hipMemcpyAsync(x.h_mm, x.d_mm, s->rows * sizeof(double), hipMemcpyDeviceToHost, x.st));
-    STREAM_TRY(hipEventRecord(x.ev_done, x.st));
-#undef STREAM_TRY
     x.n_samples = n_samples;
     x.n_valid_rows = valid_rows;
     x.max_soft = ms;
@@ -1582,7 +1508,7 @@ int tdm_stream_collect(tdm_stream *s, int32_t wait, tdm_stream_result *r)
     StreamSlot &x = s->slots[(size_t)k];
     HIP_TRY(hipSetDevice(s->device));
     if (!wait) {
-        const hipError_t e = hipEventQuery(x.ev_done);
+        const hipError_t e = hipEventQuery(x.ev_done.get());
         if (e == hipErrorNotReady) {
             (void)hipGetLastError();
             g_err = "tdm_stream_collect: the oldest step has not finished";
@@ -1590,7 +1516,7 @@ int tdm_stream_collect(tdm_stream *s, int32_t wait, tdm_stream_result *r)
         }
         HIP_TRY(e);
     } else {
-        HIP_TRY(hipEventSynchronize(x.ev_done));
+        HIP_TRY(hipEventSynchronize(x.ev_done.get()));
     }
     std::memset(r, 0, sizeof(*r));
     r->seq = s->ring.next_collect;
@@ -1599,11 +1525,11 @@ int tdm_stream_collect(tdm_stream *s, int32_t wait, tdm_stream_result *r)
     r->n_valid_rows = x.n_valid_rows;
     r->max_soft = x.max_soft;
     r->soft_bytes = x.h_soft ? (int32_t)s->soft_elem : 0;
-    r->hard = x.h_hard;
-    r->soft = x.h_soft;
-    r->n_soft = x.h_ns;
-    r->best_phase = x.h_bp;
-    r->min_margin = x.h_mm;
+    r->hard = x.h_hard.get();
+    r->soft = x.h_soft.get();
+    r->n_soft = x.h_ns.get();
+    r->best_phase = x.h_bp.get();
+    r->min_margin = x.h_mm.get();
     s->ring.commit_collect();
     return TDM_OK;
 }
@@ -1615,7 +1541,7 @@ int tdm_plan_time_begin(tdm_plan *plan)
     HIP_TRY(hipSetDevice(plan->device));
     plan->timer.release_all();
     plan->timer.on = true;
-    HIP_TRY(hipEventRecord(plan->ev0, plan->stream));
+    HIP_TRY(hipEventRecord(plan->ev0.get(), plan->stream.get()));
     return TDM_OK;
 }
 
@@ -1625,7 +1551,7 @@ int tdm_plan_time_begin_total(tdm_plan *plan)
     HIP_TRY(hipSetDevice(plan->device));
     plan->timer.release_all();
     plan->timer.on = false;
-    HIP_TRY(hipEventRecord(plan->ev0, plan->stream));
+    HIP_TRY(hipEventRecord(plan->ev0.get(), plan->stream.get()));
     return TDM_OK;
 }
 
@@ -1633,11 +1559,11 @@ int tdm_plan_time_end(tdm_plan *plan, float *elapsed_ms)
 {
     if (!plan) return fail(TDM_ERR_INVALID, "null plan");
     HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipEventRecord(plan->ev1, plan->stream));
-    HIP_TRY(hipEventSynchronize(plan->ev1));
+    HIP_TRY(hipEventRecord(plan->ev1.get(), plan->stream.get()));
+    HIP_TRY(hipEventSynchronize(plan->ev1.get()));
     plan->timer.on = false;
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, plan->ev0, plan->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, plan->ev0.get(), plan->ev1.get()));
     if (elapsed_ms) *elapsed_ms = ms;
     return TDM_OK;
 }
@@ -1650,8 +1576,8 @@ int tdm_plan_stage_times(tdm_plan *plan, int32_t max_stages, const char **names,
     int cnt[ST_COUNT] = {0};
     for (auto &r : plan->timer.recs) {
         float t = 0;
-        HIP_TRY(hipEventSynchronize(r.b));
-        HIP_TRY(hipEventElapsedTime(&t, r.a, r.b));
+        HIP_TRY(hipEventSynchronize(r.b.get()));
+        HIP_TRY(hipEventElapsedTime(&t, r.a.get(), r.b.get()));
         acc[r.stage] += t;
         cnt[r.stage]++;
     }
@@ -1741,16 +1667,18 @@ int tdm_hbm_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs)
     int rc = use_device(device);
     if (rc) return rc;
     const size_t n16 = bytes / 16;
-    ceil_f4 *a = nullptr, *b = nullptr;
-    HIP_TRY(hipMalloc((void **)&a, n16 * 16));
-    if (hipMalloc((void **)&b, n16 * 16) != hipSuccess) {
-        (void)hipFree(a);
+    DevPtr<ceil_f4> a_, b_;
+    HIP_TRY(dev_alloc(a_, n16 * 16));
+    if (dev_alloc(b_, n16 * 16) != hipSuccess) {
+        (void)hipGetLastError();
         return fail(TDM_ERR_NOMEM, "tdm_hbm_ceiling: hipMalloc");
     }
+    ceil_f4 *a = a_.get(), *b = b_.get();
     hipStream_t st = g_cur_stream;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    Event e0_, e1_;
+    HIP_TRY(event_create(e0_));
+    HIP_TRY(event_create(e1_));
+    hipEvent_t e0 = e0_.get(), e1 = e1_.get();
     (void)hipMemsetAsync(a, 0, n16 * 16, st);
     (void)hipMemsetAsync(b, 0, n16 * 16, st);
     gbs[0] = gbs[1] = gbs[2] = 0.0;
@@ -1786,10 +1714,6 @@ int tdm_hbm_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs)
             if (rate > gbs[what]) gbs[what] = rate;
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(a);
-    (void)hipFree(b);
     if (err != hipSuccess) return fail(TDM_ERR_HIP, std::string("tdm_hbm_ceiling: ") + hipGetErrorString(err));
     return TDM_OK;
 }
@@ -1801,32 +1725,24 @@ int tdm_link_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs)
     int rc = use_device(device);
     if (rc) return rc;
     bytes &= ~(size_t)4095;
-    void *h = nullptr, *d = nullptr;
-    hipStream_t s0 = nullptr, s1 = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    auto release = [&]() {
-        if (s0) (void)hipStreamSynchronize(s0);
-        if (s1) (void)hipStreamSynchronize(s1);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e2) (void)hipEventDestroy(e2);
-        if (s0) (void)hipStreamDestroy(s0);
-        if (s1) (void)hipStreamDestroy(s1);
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        (void)hipGetLastError();
-    };
-    hipError_t err = hipHostMalloc(&h, bytes, hipHostMallocDefault);
-    if (err == hipSuccess) err = hipMalloc(&d, bytes);
-    if (err == hipSuccess) err = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipStreamCreateWithFlags(&s1, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
-    if (err == hipSuccess) err = hipEventCreate(&e2);
+    HostPtr<void> h_;
+    DevPtr<void> d_;
+    Stream s0_, s1_;
+    Event e0_, e1_, e2_;
+    hipError_t err = host_alloc(h_, bytes);
+    if (err == hipSuccess) err = dev_alloc(d_, bytes);
+    if (err == hipSuccess) err = stream_create(s0_);
+    if (err == hipSuccess) err = stream_create(s1_);
+    if (err == hipSuccess) err = event_create(e0_);
+    if (err == hipSuccess) err = event_create(e1_);
+    if (err == hipSuccess) err = event_create(e2_);
     if (err != hipSuccess) {
-        release();
+        (void)hipGetLastError();
         return fail(TDM_ERR_NOMEM, std::string("tdm_link_ceiling: ") + hipGetErrorString(err));
     }
+    void *h = h_.get(), *d = d_.get();
+    hipStream_t s0 = s0_.get(), s1 = s1_.get();
+    hipEvent_t e0 = e0_.get(), e1 = e1_.get(), e2 = e2_.get();
     std::memset(h, 1, bytes);                 // (every page touched before the first copy)
     if (err == hipSuccess) err = hipMemset(d, 0, bytes);
     gbs[0] = gbs[1] = gbs[2] = 0.0;
@@ -1854,7 +1770,9 @@ int tdm_link_ceiling(int32_t device, size_t bytes, int32_t reps, double *gbs)
             gbs[what] = moved / ((double)ms * 1e-3) / 1e9;
         }
     }
-    release();
+    // (after a failure copies may still be in flight)
+    (void)hipStreamSynchronize(s0);
+    (void)hipStreamSynchronize(s1);
     if (err != hipSuccess) return fail(TDM_ERR_HIP, std::string("tdm_link_ceiling: ") + hipGetErrorString(err));
     return TDM_OK;
 }
@@ -2338,7 +2256,7 @@ namespace {
 // Scratch of the device-pointer form, one buffer per (device, stream), process-wide: launches on one stream are ordered
 // whichever thread issues them, so they can share it.  The mutex is held from the look-up to the end of the enqueue, so a
 // buffer is never replaced between another caller's look-up and its launches; an entry goes away with its stream
-// (plan_free -> sync_scratch_release), so a long-lived thread that creates and destroys plans does not pile them up.
+// (~tdm_plan -> sync_scratch_release), so a long-lived thread that creates and destroys plans does not pile them up.
 struct SyncScratch { void *p = nullptr; size_t bytes = 0; };
 struct SyncScratchMap {
     std::mutex mu;
@@ -2505,10 +2423,14 @@ int pfb_tables(int device, int D, PfbTables &tb)
                     const double a = 2.0 * M_PI * ((k * n) % M2) / M2;
                     tw[M1 * M1 + M + k * M2 + n] = make_float2((float)std::cos(a), (float)std::sin(a));
                 }
-            HIP_TRY(hipMalloc(&tb.h, h.size() * 4));
-            HIP_TRY(hipMalloc(&tb.tw, tw.size() * 8));
-            HIP_TRY(hipMemcpy(tb.h, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(tb.tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
+            DevPtr<float> dh;
+            DevPtr<float2> dtw;
+            HIP_TRY(dev_alloc(dh, h.size() * 4));
+            HIP_TRY(dev_alloc(dtw, tw.size() * 8));
+            HIP_TRY(hipMemcpy(dh.get(), h.data(), h.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dtw.get(), tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
+            tb.h = dh.release();   // (the cache keeps them for the process's lifetime)
+            tb.tw = dtw.release();
             g_pfb_cache[key] = tb;
         } else {
             tb = it->second;
@@ -2786,27 +2708,19 @@ struct tdm_channeliser {
     int64_t max_n_in = 0;
     int64_t pitch_dev = 0;                   // row pitch of d_out (host-form pushes)
     int64_t samples_in = 0, samples_out = 0; // per stream, since create / reset
-    void *hist[2] = {nullptr, nullptr};
+    DevPtr<void> hist[2];
     int cur = 0;
     int64_t hist_stride = 0;                 // bytes between the streams of a history buffer
-    void *d_in = nullptr, *d_out = nullptr;  // host-form staging
-    hipStream_t st = nullptr;                // host-form pushes
-    hipEvent_t ev_last = nullptr;
+    DevPtr<void> d_in, d_out;                // host-form staging
+    Stream st;                               // host-form pushes
+    Event ev_last;
+    ~tdm_channeliser()   // a push may still be in flight: drained before the members go
+    {
+        (void)hipSetDevice(device);
+        if (ev_last) (void)hipEventSynchronize(ev_last.get());
+        if (st) (void)hipStreamSynchronize(st.get());
+    }
 };
-
-static void channeliser_free(tdm_channeliser *ch)
-{
-    if (!ch) return;
-    (void)hipSetDevice(ch->device);
-    if (ch->ev_last) (void)hipEventSynchronize(ch->ev_last);
-    if (ch->st) (void)hipStreamSynchronize(ch->st);
-    void *dev[] = {ch->hist[0], ch->hist[1], ch->d_in, ch->d_out};
-    for (void *q : dev) if (q) (void)hipFree(q);
-    if (ch->ev_last) (void)hipEventDestroy(ch->ev_last);
-    if (ch->st) (void)hipStreamDestroy(ch->st);
-    (void)hipGetLastError();
-    delete ch;
-}
 
 int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_streams, int64_t max_n_in, int32_t device,
                            tdm_channeliser **out)
@@ -2824,7 +2738,7 @@ int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_strea
     int rc = pfb_for_m(M, fits);
     if (rc) return rc;
     if ((rc = use_device(device))) return rc;
-    std::unique_ptr<tdm_channeliser, void (*)(tdm_channeliser *)> ch(new tdm_channeliser, channeliser_free);
+    std::unique_ptr<tdm_channeliser> ch(new tdm_channeliser);
     ch->device = device;
     ch->M = M;
     ch->D = D;
@@ -2839,16 +2753,16 @@ int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_strea
     ch->pitch_dev = (max_n_in + D - 1) / D;
     ch->pitch_dev = (ch->pitch_dev + 15) / 16 * 16;
     const size_t hb = (size_t)n_streams * ch->hist_stride;
-    for (void *&h : ch->hist) {
-        HIP_TRY(hipMalloc(&h, hb));
-        HIP_TRY(hipMemset(h, 0, hb));
+    for (auto &h : ch->hist) {
+        HIP_TRY(dev_alloc(h, hb));
+        HIP_TRY(hipMemset(h.get(), 0, hb));
     }
-    HIP_TRY(hipMalloc(&ch->d_in, (size_t)n_streams * max_n_in * fb));
-    HIP_TRY(hipMalloc(&ch->d_out, (size_t)n_streams * M * ch->pitch_dev * sizeof(float2)));
-    HIP_TRY(hipStreamCreateWithFlags(&ch->st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ch->ev_last, hipEventDisableTiming));
+    HIP_TRY(dev_alloc(ch->d_in, (size_t)n_streams * max_n_in * fb));
+    HIP_TRY(dev_alloc(ch->d_out, (size_t)n_streams * M * ch->pitch_dev * sizeof(float2)));
+    HIP_TRY(stream_create(ch->st));
+    HIP_TRY(event_create(ch->ev_last, hipEventDisableTiming));
     HIP_TRY(hipStreamSynchronize(nullptr));   // (the zeroing above is done before the first push)
-    HIP_TRY(hipEventRecord(ch->ev_last, ch->st));
+    HIP_TRY(hipEventRecord(ch->ev_last.get(), ch->st.get()));
     *out = ch.release();
     return TDM_OK;
 }
@@ -2868,35 +2782,35 @@ int tdm_channeliser_push(tdm_channeliser *ch, const void *iq, int64_t n_in, floa
     const int64_t pitch = out_pitch ? out_pitch : p.n_out;
     const int fb = pfb_fmt_bytes(ch->fmt);
     HIP_TRY(hipSetDevice(ch->device));
-    hipStream_t st = device_pointers ? g_cur_stream : ch->st;
-    HIP_TRY(hipStreamWaitEvent(st, ch->ev_last, 0));   // behind the previous push, on whatever stream it ran
+    hipStream_t st = device_pointers ? g_cur_stream : ch->st.get();
+    HIP_TRY(hipStreamWaitEvent(st, ch->ev_last.get(), 0));   // behind the previous push, on whatever stream it ran
     const void *src = iq;
     float2 *dst = (float2 *)out;
     int64_t dpitch = pitch;
     if (!device_pointers) {
-        HIP_TRY(hipMemcpyAsync(ch->d_in, iq, (size_t)ch->n_streams * n_in * fb, hipMemcpyHostToDevice, st));
-        src = ch->d_in;
-        dst = (float2 *)ch->d_out;
+        HIP_TRY(hipMemcpyAsync(ch->d_in.get(), iq, (size_t)ch->n_streams * n_in * fb, hipMemcpyHostToDevice, st));
+        src = ch->d_in.get();
+        dst = (float2 *)ch->d_out.get();
         dpitch = ch->pitch_dev;
     }
     int rc;
     if (p.n_out > 0) {
-        const PfbCarry carry{ch->hist[ch->cur], ch->hist_stride, p.hist_valid, p.o, p.s_base};
+        const PfbCarry carry{ch->hist[ch->cur].get(), ch->hist_stride, p.hist_valid, p.o, p.s_base};
         PfbLaunchOp op{ch->device, src, ch->fmt, n_in, D, dst, p.n_out, dpitch, ch->n_streams, st, false, &carry};
         if ((rc = pfb_for_m(M, op))) return rc;
     }
     const dim3 hgrid((unsigned)((ch->L - 1 + 255) / 256), (unsigned)ch->n_streams);
     if (ch->fmt == TDM_CF32)
-        hipLaunchKernelGGL(k_pfb_hist<uint2>, hgrid, dim3(256), 0, st, (const uint2 *)src, n_in, (const uint2 *)ch->hist[ch->cur],
-                           (uint2 *)ch->hist[ch->cur ^ 1], ch->hist_stride / fb, n_in, ch->L);
+        hipLaunchKernelGGL(k_pfb_hist<uint2>, hgrid, dim3(256), 0, st, (const uint2 *)src, n_in, (const uint2 *)ch->hist[ch->cur].get(),
+                           (uint2 *)ch->hist[ch->cur ^ 1].get(), ch->hist_stride / fb, n_in, ch->L);
     else
         hipLaunchKernelGGL(k_pfb_hist<uint16_t>, hgrid, dim3(256), 0, st, (const uint16_t *)src, n_in,
-                           (const uint16_t *)ch->hist[ch->cur], (uint16_t *)ch->hist[ch->cur ^ 1], ch->hist_stride / fb, n_in, ch->L);
+                           (const uint16_t *)ch->hist[ch->cur].get(), (uint16_t *)ch->hist[ch->cur ^ 1].get(), ch->hist_stride / fb, n_in, ch->L);
     HIP_TRY(hipGetLastError());
     if (!device_pointers && p.n_out > 0)
-        HIP_TRY(hipMemcpy2DAsync(out, (size_t)pitch * sizeof(float2), ch->d_out, (size_t)dpitch * sizeof(float2),
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)pitch * sizeof(float2), ch->d_out.get(), (size_t)dpitch * sizeof(float2),
                                  (size_t)p.n_out * sizeof(float2), (size_t)ch->n_streams * M, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ch->ev_last, st));
+    HIP_TRY(hipEventRecord(ch->ev_last.get(), st));
     if (!device_pointers) HIP_TRY(hipStreamSynchronize(st));
     ch->cur ^= 1;
     ch->samples_in += n_in;
@@ -2922,7 +2836,7 @@ int tdm_channeliser_position(tdm_channeliser *ch, int64_t *samples_in, int64_t *
 
 int tdm_channeliser_destroy(tdm_channeliser *ch)
 {
-    channeliser_free(ch);
+    delete ch;
     return TDM_OK;
 }
 
