@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: IQ -> pi/4-DQPSK hard symbols (reference-parity mode).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--carriers C] [--chunk S] [--fmt cu8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--carriers C] [--chunk S] [--fmt cu8] [--full]
 
 One "step" = one pass of SignalProcessor.process over a batch of C independent 2.4 MS/s carriers
 of S samples each per GPU (1024 carriers x 262144-sample chunks across
@@ -9,6 +9,12 @@ of S samples each per GPU (1024 carriers x 262144-sam
 collective).  Inputs are resident in HBM before the timed region.  For N > 1 the driver launches
 one process per GPU with torch.distributed.run; RCCL is used only for the barrier and the
 max-over-ranks of the elapsed time.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write
+--dump-outputs, print the line.  --full adds everything else the bench measures and checks: the
+per-kernel pass and the roofline (HBM ceilings and traffic counted on this box), the output digest
+against the oracle-pinned one, the CPU baselines, the one-plan figure, the single-carrier / tetra /
+channeliser / wideband legs at N = 1 and the weak-scaling side run at N > 1.
 
 Prints ONE JSON line (rank 0).
 """
@@ -460,6 +466,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, at most "
                          "64 MB: a fixed seeded sample of the carriers beyond that; rank 0's carriers); see dump_outputs()")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything else the bench measures and checks (see the module docstring); "
+                         "--no-cpu-baseline and --no-extra leave parts of it out.  The --mode legs report in full either way")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -602,44 +611,49 @@ def main():
     ev_ms = bd.time_end()
     barrier()
     dt = time.perf_counter() - t0
-    # --dump-outputs: the last timed step's outputs, downloaded before anything else runs on the plans
-    dumped = dump_outputs(args.dump_outputs, *bd.download()) if (args.dump_outputs and rank == 0) else None
-    # the per-kernel pass: the same `steps` passes again with a HIP-event pair around every launch (the roofline's kernel
-    # time).  The events themselves cost ~5 us per launch, which is why this is not the region `value` is taken from.
-    bd.time_begin(per_stage=True)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        bd.enqueue()
-    ev_ms_staged = bd.time_end()
-    barrier()
-    dt_staged = time.perf_counter() - t1
-    stage_ms = bd.stage_times()   # average per launch over the per-kernel pass
+    # the last timed step's outputs, downloaded before anything else runs on the plans: --dump-outputs writes them, and a
+    # plain run counts its symbols in them
+    last = bd.download()
+    dumped = dump_outputs(args.dump_outputs, *last) if (args.dump_outputs and rank == 0) else None
+    mismatch, fast_shift_report = False, None
+    if args.full:
+        # the per-kernel pass: the same `steps` passes again with a HIP-event pair around every launch (the roofline's kernel
+        # time).  The events themselves cost ~5 us per launch, which is why this is not the region `value` is taken from.
+        bd.time_begin(per_stage=True)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            bd.enqueue()
+        bd.time_end()
+        barrier()
+        dt_staged = time.perf_counter() - t1
+        stage_ms = bd.stage_times()   # average per launch over the per-kernel pass
+        last = bd.download()
 
-    hard, soft, n_soft, bp, mm = bd.download()
+    hard, soft, n_soft, bp, mm = last
     sym_per_step = int(np.sum(np.maximum(n_soft.astype(np.int64) - 1, 0)))
-    # the output of the last timed step is checked, not just counted: its digest must equal the one pinned to the oracle --
-    # and so must the last output of every other plan that took steps in turn with it
-    dkey = digest_key(per_chunk, args.chunk, args.fmt, args.rate, rank, args.shared) + (f":chunks{tchunks}" if tchunks > 1 else "") + (f":strong{lo}-{hi}of{args.total_carriers}" if strong and world > 1 else "")
-    digest, want = output_digest(hard, n_soft, bp), expected_digest(dkey)
-    if hasattr(bd, "download_all"):
-        for o in bd.download_all():
-            d2 = output_digest(o[0], o[2], o[3])
-            if d2 != digest:
-                digest = "plans disagree: " + digest + " / " + d2
-                break
-            mm = np.minimum(mm, o[4])
-    if args.zero_foff or args.pmc_child:
-        want = None
-    mismatch = want is not None and digest != want
-    fast_shift_report = None
-    if fast_shift:
-        # the guard of the fast pre-shift: no carrier's smallest decision margin within reach of the phase rounding it skips
-        # (1e-8 rad is 100x that rounding), and -- below -- the digest pinned to the ORACLE's exact-phase decisions
-        fast_shift_report = {"min_margin_rad": float(np.min(mm)), "guard_rad": 1e-8, "carriers_below_guard": int(np.sum(mm < 1e-8))}
-    output_check = {"key": dkey, "sha256": digest,
-                    "status": "matches oracle-pinned digest" if want == digest else
-                              ("not compared" if (args.zero_foff or args.pmc_child) else
-                               ("no pinned digest for this workload" if want is None else "DIFFERS from the oracle-pinned digest"))}
+    if args.full:
+        # the output of the last step is checked, not just counted: its digest must equal the one pinned to the oracle --
+        # and so must the last output of every other plan that took steps in turn with it
+        dkey = digest_key(per_chunk, args.chunk, args.fmt, args.rate, rank, args.shared) + (f":chunks{tchunks}" if tchunks > 1 else "") + (f":strong{lo}-{hi}of{args.total_carriers}" if strong and world > 1 else "")
+        digest, want = output_digest(hard, n_soft, bp), expected_digest(dkey)
+        if hasattr(bd, "download_all"):
+            for o in bd.download_all():
+                d2 = output_digest(o[0], o[2], o[3])
+                if d2 != digest:
+                    digest = "plans disagree: " + digest + " / " + d2
+                    break
+                mm = np.minimum(mm, o[4])
+        if args.zero_foff or args.pmc_child:
+            want = None
+        mismatch = want is not None and digest != want
+        if fast_shift:
+            # the guard of the fast pre-shift: no carrier's smallest decision margin within reach of the phase rounding it skips
+            # (1e-8 rad is 100x that rounding), and -- below -- the digest pinned to the ORACLE's exact-phase decisions
+            fast_shift_report = {"min_margin_rad": float(np.min(mm)), "guard_rad": 1e-8, "carriers_below_guard": int(np.sum(mm < 1e-8))}
+        output_check = {"key": dkey, "sha256": digest,
+                        "status": "matches oracle-pinned digest" if want == digest else
+                                  ("not compared" if (args.zero_foff or args.pmc_child) else
+                                   ("no pinned digest for this workload" if want is None else "DIFFERS from the oracle-pinned digest"))}
 
     # (a rank whose check failed still takes part in the reductions: the failure count is reduced with the job and ALL
     # ranks stop together below; leaving early would strand the others inside ncclAllReduce)
@@ -654,7 +668,7 @@ def main():
 
     info_n_dec, info_engine = int(bd.info.n_dec), int(bd.info.dec_engine)
     weak = None
-    if args.weak_side:
+    if args.weak_side and args.full:
         # BASELINE config 4's other reading, beside the headline: every rank its own 1024 carriers (8192 on 8 GPUs)
         bd.close()
         bd = None
@@ -662,29 +676,6 @@ def main():
     if rank == 0:
         value = total_sym_per_step * args.steps / dt / 1e6
         sym_rate_per_carrier = SAMPLE_RATE / 10 / 13   # 18461.5 sym/s in reference mode @2.4 MS/s
-        k1_ms = stage_ms.get("dec_block", float("nan"))
-        samples_per_launch = carriers * args.chunk
-        in_bytes = {"cu8": 2, "cf32": 8, "cf64": 16}[args.fmt]
-        n_dec = info_n_dec
-        k1_bytes = samples_per_launch * in_bytes + carriers * n_dec * 16
-        contract_tf = samples_per_launch * FLOP_PER_INPUT_SAMPLE / (k1_ms * 1e-3) / 1e12
-        # executed flops: exact for the raw-byte kernel (dec_engine 3, the bench's case); the double-based kernel executes
-        # 52.5 FMAs per sample and the cascade engine 133 issue slots: other engines report the same field from their counts
-        # (a call with an input-rate pre-shift -- --shared -- runs the double-based kernel whatever the batch size: the raw-byte
-        # kernel works on integers, and a rotated sample is none; tdm_plan_info cannot know the call's arguments)
-        engine = 2 if (args.shared and info_engine == 3) else info_engine
-        # --shared adds, per input sample, the conversion (4 flop) and the input-rate NCO that reproduces the reference's own
-        # rounding of its phase (NcoRunT: Markstein quotient 10, phase 1, phasor advance 6, correction 7, rotation 6: ~35 flop)
-        exec_flop = {3: EXECUTED_FLOP_PER_INPUT_SAMPLE, 2: 105.0, 1: 266.0}.get(engine, EXECUTED_FLOP_PER_INPUT_SAMPLE) + ((16.0 if fast_shift else 39.0) if args.shared else 0.0)
-        executed_tf = samples_per_launch * exec_flop / (k1_ms * 1e-3) / 1e12
-        irreducible_tf = samples_per_launch * IRREDUCIBLE_FLOP_PER_INPUT_SAMPLE / (k1_ms * 1e-3) / 1e12
-        ceil = hbm_ceiling(local_rank) if (world == 1 and not args.pmc_child) else {}
-        traffic, traffic_src, traffic_detail = None, None, None
-        if world == 1 and not args.pmc_child:
-            child = ["--carriers", str(carriers), "--chunk", str(args.chunk), "--fmt", args.fmt, "--rate", repr(args.rate),
-                     "--no-cpu-baseline", "--no-extra", "--depth", str(depth)] + (["--shared", "--chunks", str(tchunks)] if args.shared else [])
-            traffic, traffic_src, traffic_detail = traffic_now(child, "k_pz_raw<" if engine == 3 else ("k_pz_block<" if engine == 2 else "k_zp_block<"),
-                                                               samples_per_launch, args.fmt, "k1")
         total = args.total_carriers if strong else carriers * world
         out = {
             "metric": "Msymbols/s demodulated (reference-parity mode, hard symbols written)",
@@ -710,63 +701,92 @@ def main():
                                            "how": ("one plan, one stream: steps strictly one after the other" if depth == 1 else
                                                    f"{depth} plans of the whole batch take the steps in turn, each on its own stream and work buffers "
                                                    "(tetraear_amd.batch.PipelinedBatchDemodulator): a step's carries / low-rate stage / finish run beside "
-                                                   "the next step's decimator; every launch is the full batch, every plan's output is checked (digest below)")},
+                                                   "the next step's decimator; every launch is the full batch"
+                                                   + (", every plan's output is checked (digest below)" if args.full else ""))},
                        "mode": "reference", "parallelism": f"carriers sharded over {world} GPU(s), no data-path collective",
                        "collective": collective},
             "realtime_carriers": value * 1e6 / sym_rate_per_carrier,
-            "output_check": output_check,
             "pre_shift": (None if not args.shared else
-                          ({"phase": "ideal ramp from an exactly anchored sample per lane (plan option fast_pre_shift)", **fast_shift_report}
+                          ({"phase": "ideal ramp from an exactly anchored sample per lane (plan option fast_pre_shift)", **(fast_shift_report or {})}
                            if fast_shift else {"phase": "the reference's rounding of theta reproduced sample by sample"})),
             "rccl_ranks": world if group is not None else 0,
             "plan_create_ms": plan_create_ms,
             "settle_steps": settle_steps,   # untimed passes before the warm-up (clock ramp after idle)
             "event_ms_per_step_rank0": ev_ms / args.steps,
-            "ms_per_step_per_kernel_pass_rank0": dt_staged / args.steps * 1e3,   # same steps with events around every launch
-            "stage_ms_per_launch": stage_ms,
-            "stage_timing": ("HIP events around every launch on its plan's stream" if depth == 1 else
-                             f"HIP events around every launch on its plan's stream, the steps ordered ONE AFTER THE OTHER on the device in this pass "
-                             "(tdm_plan_wait_for: every launch alone on the device); in the timed region consecutive steps overlap, so a launch "
-                             "there takes longer than here while a step takes less than the sum of its launches"),
-            "roofline": {
-                "kernel": ("k_pz_raw<10,12,27> (zero-phase Chebyshev-8 decimator in parallel form: causal + anticausal all-pole banks on the raw samples)"
-                           if engine == 3 else
-                           ("k_pz_block<shift> (the same decimator on doubles, every sample first rotated by its carrier's input-rate NCO: frequency_shift(x, f_k) of the shared stream)"
-                            if args.shared else
-                            "k_pz_block (the same decimator with the samples held as doubles: few carriers, or a wire format other than cu8)")
-                           if engine == 2 else "k_zp_block (cascade engine)"),
-                "bound": "valu_fp64",
-                # frac = what the fp64 vector ALUs execute over their peak (never > 1); round 2 reported SURVEY 8(d)'s
-                # operation count over the measured time here, which the parallel form undercuts (1.02 "of peak")
-                "achieved": executed_tf,
-                "peak": PEAK_FP64_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": executed_tf / PEAK_FP64_TFLOPS,
-                "flop_per_input_sample": exec_flop,
-                "avg_launch_ms": k1_ms,
-                "irreducible": {"flop_per_input_sample": IRREDUCIBLE_FLOP_PER_INPUT_SAMPLE, "achieved": irreducible_tf,
-                                "frac": irreducible_tf / PEAK_FP64_TFLOPS,
-                                "note": "the recurrences alone (2 FMAs per real sample, pole pair and direction): what no form of this filter avoids"},
-                "contract_survey_8d": {"flop_per_input_sample": FLOP_PER_INPUT_SAMPLE, "algorithmic_flop_per_launch": samples_per_launch * FLOP_PER_INPUT_SAMPLE,
-                                       "rate": contract_tf, "rate_over_peak": contract_tf / PEAK_FP64_TFLOPS,
-                                       "note": "SURVEY 8(d) prices the cascade (150 flop/sample); the parallel form executes 84.7, so this "
-                                               "rate can exceed the ALU peak and is NOT a fraction of anything the kernel does"},
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "traffic_detail": traffic_detail,
-                "hbm": {"achieved": k1_bytes / (k1_ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                        "frac": k1_bytes / (k1_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                        "peak_measured": ceil.get("copy"),
-                        "frac_of_measured": (k1_bytes / (k1_ms * 1e-3) / 1e9 / ceil["copy"]) if "copy" in ceil else None,
-                        "algorithmic_bytes_per_launch": k1_bytes},
-                "note": "no MFMA on this path; the kernel is fp64-vector-ALU bound (78.6 TFLOP/s = 16 fp64 FMA lanes per SIMD and "
-                        "clock); the HBM view of the same launch is under 'hbm'",
-            },
-            "hbm_ceiling_measured": ceil or None,
+            "full": args.full,   # False: the side measurements and checks were left out (see --full)
         }
+        if args.full:
+            k1_ms = stage_ms.get("dec_block", float("nan"))
+            samples_per_launch = carriers * args.chunk
+            in_bytes = {"cu8": 2, "cf32": 8, "cf64": 16}[args.fmt]
+            n_dec = info_n_dec
+            k1_bytes = samples_per_launch * in_bytes + carriers * n_dec * 16
+            contract_tf = samples_per_launch * FLOP_PER_INPUT_SAMPLE / (k1_ms * 1e-3) / 1e12
+            # executed flops: exact for the raw-byte kernel (dec_engine 3, the bench's case); the double-based kernel executes
+            # 52.5 FMAs per sample and the cascade engine 133 issue slots: other engines report the same field from their counts
+            # (a call with an input-rate pre-shift -- --shared -- runs the double-based kernel whatever the batch size: the raw-byte
+            # kernel works on integers, and a rotated sample is none; tdm_plan_info cannot know the call's arguments)
+            engine = 2 if (args.shared and info_engine == 3) else info_engine
+            # --shared adds, per input sample, the conversion (4 flop) and the input-rate NCO that reproduces the reference's own
+            # rounding of its phase (NcoRunT: Markstein quotient 10, phase 1, phasor advance 6, correction 7, rotation 6: ~35 flop)
+            exec_flop = {3: EXECUTED_FLOP_PER_INPUT_SAMPLE, 2: 105.0, 1: 266.0}.get(engine, EXECUTED_FLOP_PER_INPUT_SAMPLE) + ((16.0 if fast_shift else 39.0) if args.shared else 0.0)
+            executed_tf = samples_per_launch * exec_flop / (k1_ms * 1e-3) / 1e12
+            irreducible_tf = samples_per_launch * IRREDUCIBLE_FLOP_PER_INPUT_SAMPLE / (k1_ms * 1e-3) / 1e12
+            ceil = hbm_ceiling(local_rank) if (world == 1 and not args.pmc_child) else {}
+            traffic, traffic_src, traffic_detail = None, None, None
+            if world == 1 and not args.pmc_child:
+                # (the child is a full run, so that its launches are those of this run's timed region and per-kernel pass)
+                child = ["--carriers", str(carriers), "--chunk", str(args.chunk), "--fmt", args.fmt, "--rate", repr(args.rate),
+                         "--no-cpu-baseline", "--no-extra", "--full", "--depth", str(depth)] + (["--shared", "--chunks", str(tchunks)] if args.shared else [])
+                traffic, traffic_src, traffic_detail = traffic_now(child, "k_pz_raw<" if engine == 3 else ("k_pz_block<" if engine == 2 else "k_zp_block<"),
+                                                                   samples_per_launch, args.fmt, "k1")
+            out.update({
+                "output_check": output_check,
+                "ms_per_step_per_kernel_pass_rank0": dt_staged / args.steps * 1e3,   # same steps with events around every launch
+                "stage_ms_per_launch": stage_ms,
+                "stage_timing": ("HIP events around every launch on its plan's stream" if depth == 1 else
+                                 f"HIP events around every launch on its plan's stream, the steps ordered ONE AFTER THE OTHER on the device in this pass "
+                                 "(tdm_plan_wait_for: every launch alone on the device); in the timed region consecutive steps overlap, so a launch "
+                                 "there takes longer than here while a step takes less than the sum of its launches"),
+                "roofline": {
+                    "kernel": ("k_pz_raw<10,12,27> (zero-phase Chebyshev-8 decimator in parallel form: causal + anticausal all-pole banks on the raw samples)"
+                               if engine == 3 else
+                               ("k_pz_block<shift> (the same decimator on doubles, every sample first rotated by its carrier's input-rate NCO: frequency_shift(x, f_k) of the shared stream)"
+                                if args.shared else
+                                "k_pz_block (the same decimator with the samples held as doubles: few carriers, or a wire format other than cu8)")
+                               if engine == 2 else "k_zp_block (cascade engine)"),
+                    "bound": "valu_fp64",
+                    # frac = what the fp64 vector ALUs execute over their peak (never > 1); round 2 reported SURVEY 8(d)'s
+                    # operation count over the measured time here, which the parallel form undercuts (1.02 "of peak")
+                    "achieved": executed_tf,
+                    "peak": PEAK_FP64_TFLOPS,
+                    "unit": "TFLOP/s",
+                    "frac": executed_tf / PEAK_FP64_TFLOPS,
+                    "flop_per_input_sample": exec_flop,
+                    "avg_launch_ms": k1_ms,
+                    "irreducible": {"flop_per_input_sample": IRREDUCIBLE_FLOP_PER_INPUT_SAMPLE, "achieved": irreducible_tf,
+                                    "frac": irreducible_tf / PEAK_FP64_TFLOPS,
+                                    "note": "the recurrences alone (2 FMAs per real sample, pole pair and direction): what no form of this filter avoids"},
+                    "contract_survey_8d": {"flop_per_input_sample": FLOP_PER_INPUT_SAMPLE, "algorithmic_flop_per_launch": samples_per_launch * FLOP_PER_INPUT_SAMPLE,
+                                           "rate": contract_tf, "rate_over_peak": contract_tf / PEAK_FP64_TFLOPS,
+                                           "note": "SURVEY 8(d) prices the cascade (150 flop/sample); the parallel form executes 84.7, so this "
+                                                   "rate can exceed the ALU peak and is NOT a fraction of anything the kernel does"},
+                    "traffic": traffic,
+                    "traffic_source": traffic_src,
+                    "traffic_detail": traffic_detail,
+                    "hbm": {"achieved": k1_bytes / (k1_ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                            "frac": k1_bytes / (k1_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                            "peak_measured": ceil.get("copy"),
+                            "frac_of_measured": (k1_bytes / (k1_ms * 1e-3) / 1e9 / ceil["copy"]) if "copy" in ceil else None,
+                            "algorithmic_bytes_per_launch": k1_bytes},
+                    "note": "no MFMA on this path; the kernel is fp64-vector-ALU bound (78.6 TFLOP/s = 16 fp64 FMA lanes per SIMD and "
+                            "clock); the HBM view of the same launch is under 'hbm'",
+                },
+                "hbm_ceiling_measured": ceil or None,
+            })
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if not args.no_cpu_baseline and world == 1 and not args.pmc_child:   # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.pmc_child:   # reported on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.chunk)
             try:
                 out["cpu_baseline_allcore"] = cpu_baseline_allcore(args.chunk)
@@ -774,7 +794,7 @@ def main():
                 out["cpu_baseline_allcore"] = {"error": str(e)}
     if bd is not None:
         bd.close()
-    if rank == 0:
+    if rank == 0 and args.full:
         if weak is not None:
             out["weak"] = weak
         if (world == 1 and not args.no_extra and not strong and not args.shared and not args.pmc_child and args.fmt == "cu8"

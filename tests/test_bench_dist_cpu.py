@@ -80,6 +80,8 @@ def _rank(rank, world, port, bad_rank, q, strong=False):
         bench.expected_digest = lambda key: ("0" * 64 if f"rank{bad_rank}" in key else None)
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--carriers", "4", "--chunk", "4096",
                 "--no-cpu-baseline"]
+    if bad_rank is not None or strong:
+        sys.argv.append("--full")   # (the output check runs in a full run only)
     if strong:
         # BASELINE config 4's split: ONE job of 8 carriers over the ranks; the slice digests are pinned under keys that
         # name the slice (":strong{lo}-{hi}of{T}") -- here pinned to what the stand-in device returns for that rank
@@ -137,6 +139,7 @@ def test_two_rank_bench_prints_one_line_with_job_totals():
     # symbols of both ranks: 4 carriers x (29 + 30), over the slower rank's elapsed time
     assert d["value"] > 0 and d["config"]["carriers_per_gpu"] == 4
     assert "cpu_baseline" not in d and "tetra" not in d        # N = 1 only
+    assert d["full"] is False and "output_check" not in d and "roofline" not in d   # a plain run: the headline only
 
 
 @pytest.mark.timeout(180)
@@ -208,7 +211,8 @@ def test_bench_gpus_2_default_workload_is_config_4_as_written():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(TDM_RCCL_LIB=STUB, TDM_BENCH_TEST_HOOK=os.path.join(HERE, "bench_fake_device.py"), PYTHONPATH=ROOT,
                TDM_BENCH_NO_PINNED="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--chunk", "4096", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--chunk", "4096", "--no-cpu-baseline",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=200, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -224,3 +228,9 @@ def test_bench_gpus_2_default_workload_is_config_4_as_written():
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["scaling"] == "weak" and d["total_carriers"] == 8 and "weak" not in d
+    # a plain run (no --full): the same strong-scaling headline, without the weak-scaling side run or the output check
+    r = subprocess.run(cmd[:-1], env=env, capture_output=True, text=True, timeout=200, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["scaling"] == "strong" and d["total_carriers"] == 1024 and d["config"]["carriers_per_gpu"] == 512
+    assert "weak" not in d and "output_check" not in d and d["full"] is False

@@ -82,6 +82,25 @@ def test_dump_outputs_samples_rows_beyond_the_limit(tmp_path):
     assert np.array_equal(np.load(tmp_path / "a" / "best_phase.npy"), bp[sel]) and np.array_equal(np.load(tmp_path / "a" / "min_margin.npy"), mm[sel])
 
 
+@pytest.mark.timeout(240)
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """a plain run prints the headline fields and leaves the per-kernel pass, the roofline and the output check to --full"""
+    headline = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"}
+    side = {"output_check", "ms_per_step_per_kernel_pass_rank0", "stage_ms_per_launch", "roofline", "hbm_ceiling_measured"}
+    r = _run_bench(tmp_path, "--steps", "3", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    plain = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert headline <= set(plain) and not side & set(plain) and plain["full"] is False
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["dtype"] == "f64"
+    r = _run_bench(tmp_path, "--steps", "3", "--warmup", "1", "--full")
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert headline | side <= set(full) and full["full"] is True
+    assert full["stage_ms_per_launch"]["dec_block"] == 0.5 and full["roofline"]["avg_launch_ms"] == 0.5
+    assert full["output_check"]["status"] == "no pinned digest for this workload"
+    assert {k: full[k] for k in ("metric", "unit", "higher_is_better", "dtype")} == {k: plain[k] for k in ("metric", "unit", "higher_is_better", "dtype")}
+
+
 def test_steps_below_one_are_refused(tmp_path):
     r = _run_bench(tmp_path, "--steps", "0")
     assert r.returncode != 0 and "--steps" in r.stderr
