@@ -267,7 +267,7 @@ struct RawLoaderRT {
 
 // ------------------------------------------------------------------------------------------
 // Block body: one wavefront = one block of 64 lanes x L samples, L = Q*S.
-//   Comm: edge_slots() -> PzEdgeGeom<L,EDGE>::kDoubles doubles of wavefront-private scratch;
+//   Comm: edge_slots() -> PzEdgeGeom<L,EDGE>::kDoubles doubles of wavefront-private scratch (pz_raw_body: PzRawScratch);
 //   shfl_up2<2> / shfl_down2<2> as in zp_block_body.
 // ------------------------------------------------------------------------------------------
 // Phases 2 and 3 of a block, shared by the kernels that differ in how a lane holds its samples: scans of the lane
@@ -524,8 +524,10 @@ TDM_HD void pz_block_body(const ZpParams &P, const Loader &ld, Comm &cm, int lan
 // ------------------------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TDM_OPAQUE_V(x) asm volatile("" : "+v"(x))
+#define TDM_PIN_S(x) asm volatile("" : "+s"(x))   // a scalar-loaded value has to have arrived here
 #else
 #define TDM_OPAQUE_V(x)
+#define TDM_PIN_S(x)
 #endif
 // OPAQUE: the second conversion of a sample (other direction, many steps later) must not be recognised as the same
 // computation -- the compiler would keep the first result alive across the loop instead of converting again
@@ -620,7 +622,222 @@ TDM_HD void pz_raw_sample(const void *rowp, int64_t k, int &re, int &im)
     }
 }
 
-template <int Q, int S, int EDGE, int FMT8, bool WIDE, class Comm>
+// ------------------------------------------------------------------------------------------
+// Phase 1 of a narrow block in the FOLDED form: the banks are stepped only at the output rate.  A window of Q samples
+// W_j = x[Q t + 1 + j] moves the causal state v = (w[n], w[n-1]) from n = Q t to Q t + Q and the anticausal state
+// u[t] = (w'[Q t + 1], w'[Q t + 2]) from u[t + 1] to u[t]:
+//     v[Q t + Q] = M v[Q t] + sum_j gamma_{Q-1-j} W_j,      u[t] = M u[t + 1] + sum_j gamma_j W_j,      M = C^Q.
+// Both banks have the same poles, so the two sums are mirror images: with s_j = W_j + W_{Q-1-j}, d_j = W_j - W_{Q-1-j}
+// (exact on the integers) and the host's folded coefficients (PzLayout::off_fold)
+//     S = sum_{j < Q/2} (gamma_j + gamma_{Q-1-j})/2 s_j,   A = sum_{j < Q/2} (gamma_j - gamma_{Q-1-j})/2 d_j,
+// the anticausal sum is S + A and the causal one S - A: Q multiply-adds per state component for both directions, against
+// 2 Q for the per-sample recurrences, and a byte is converted once.  The windows are taken in ascending order, once.  The
+// anticausal states, which chain downwards, come per SEGMENT of at most kFoldSeg windows from ascending prefix sums
+//     Pf[t] = sum_{t' < t} M^t' G_t'  (G = S + A),      u[t] = M^-t (Pf[n] + M^n u_in - Pf[t]);
+// the output takes -(ka^T M^-t) Pf[t] when window t is processed and +(ka^T M^-t) (Pf[n] + M^n u_in) once the later
+// segments are known.  M^-t grows like |p|^(-Q t): segments are short to keep that below 2^5 for the fastest pair.
+// The lane's samples past the last window and its first sample take plain recurrence steps.  End states leave in the
+// per-sample form's representation: (w[L-1], w[L-2]) and (w'[0], w'[1]).
+// ------------------------------------------------------------------------------------------
+template <int Q>
+struct PzRawFold { static constexpr bool value = Q == PzLayout::kFoldQ; };
+// The first segment's totals (16 doubles per lane) wait for the end of the lane in the wavefront's LDS scratch
+// (Comm::edge_slots(), which a narrow block does not otherwise use): at the last windows the register file holds two
+// finished segments' totals, the running prefix, both banks' states, all outputs and a window's sums -- 272 registers.
+constexpr int kPzFoldStash = 2 * 2 * PzLayout::kMaxPairs * kWave;
+// doubles of wavefront-private scratch behind Comm::edge_slots() that pz_raw_body needs
+template <int Q, int S, int EDGE, bool FOLD>
+struct PzRawScratch {
+    static constexpr int kEdge = PzEdgeGeom<Q * S, EDGE>::kDoubles;
+    static constexpr int kDoubles = (FOLD && PzRawFold<Q>::value && kPzFoldStash > kEdge) ? kPzFoldStash : kEdge;
+};
+
+template <int Q, int S, int FMT8>
+TDM_HD void pz_raw_fold_lane(const ZpParams &P, const uint32_t *raw, double *stash, double (*zr)[2], double (*zq)[2],
+                             double (*ur)[2], double (*uq)[2], double *yr, double *yi)
+{
+    typedef PzLayout LY;
+    constexpr int NP = LY::kMaxPairs, L = Q * S, H = Q / 2, NW = S - 1, SEG = LY::kFoldSeg, NSEG = (NW + SEG - 1) / SEG;
+    static_assert(Q == LY::kFoldQ && S >= 2, "folded tables exist for this factor only");
+    static_assert(NSEG <= 3, "kPzFoldStash holds ONE segment's totals: a longer lane would keep the others' in registers and spill");
+    const double *fold = P.pz + LY::off_fold(S);
+    const auto pz = TDM_CPTR(P.pz);
+    double xfr, xfq, xbr, xbq;
+    pz_raw_slot_init(xfr); pz_raw_slot_init(xfq); pz_raw_slot_init(xbr); pz_raw_slot_init(xbq);
+    const double dxf = pz[LY::off_fold_dx(S)];   // (the direct term of output t + 1 is formed in window t, from its last sample)
+    double vr[NP][2], vq[NP][2];           // causal (w[Q t], w[Q t - 1])
+    double pr[NSEG][NP][2], pq[NSEG][NP][2];   // the segments' prefix sums; after a segment's last window its total
+    {
+        // (slots of its own: a value that stays alive would have the window loop's slots copied at every conversion)
+        double x0r, x0q;
+        pz_raw_slot_init(x0r); pz_raw_slot_init(x0q);
+        pz_raw_cvt<FMT8, false, true>(raw, 0, x0r, x0q);
+#pragma unroll
+        for (int s = 0; s < NP; ++s) { vr[s][0] = x0r; vr[s][1] = 0; vq[s][0] = x0q; vq[s][1] = 0; }
+        yr[0] = dxf * x0r;
+        yi[0] = dxf * x0q;
+        TDM_PIN(yr[0]); TDM_PIN(yi[0]);   // (every output accumulation is pinned where it stands, see TDM_PIN)
+    }
+    // The constants of a (window, pair) step come by scalar loads in two parts, each fetched while the part before it
+    // computes: A = the pair's folded coefficients (block sums), B = M, the output taps and the segment row (state
+    // updates).  Both parts of two pairs do not fit the scalar registers; a part fetched only when it is needed leaves
+    // the vector pipe waiting on the scalar cache at every step.
+    auto load_a = [&](int s, double *o) {
+        const double *cp = fold + s * LY::kFoldStride;
+        TDM_OPAQUE_SPTR(cp);   // (opaque: keeps all pairs' constants from being fetched at once)
+        const auto c = TDM_CPTR(cp);
+#pragma unroll
+        for (int k = 0; k < 4 * H; ++k) o[k] = c[k];
+    };
+    auto load_b = [&](int s, int tl, double *o) {
+        const double *cp = fold + s * LY::kFoldStride;
+        TDM_OPAQUE_SPTR(cp);
+        const auto c = TDM_CPTR(cp);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = c[LY::kfM + k];   // M, causal taps, (anticausal taps: unused here)
+        if (tl > 0) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o[8 + k] = c[LY::kfSeg + 6 * (tl - 1) + k];
+        }
+    };
+    double ca[4 * H], cb[14];
+    load_a(0, ca);
+#pragma unroll
+    for (int t = 0; t < NW; ++t) {
+        const int seg = t / SEG, tl = t % SEG;
+        double sr[H], dr[H], sq[H], dq[H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            pz_raw_cvt<FMT8, false, true>(raw, t * Q + 1 + j, xfr, xfq);
+            pz_raw_cvt<FMT8, false, true>(raw, t * Q + Q - j, xbr, xbq);
+            if (j == 0) { yr[t + 1] = dxf * xbr; yi[t + 1] = dxf * xbq; TDM_PIN(yr[t + 1]); TDM_PIN(yi[t + 1]); }
+            sr[j] = xfr + xbr; dr[j] = xfr - xbr;
+            sq[j] = xfq + xbq; dq[j] = xfq - xbq;
+        }
+#pragma unroll
+        for (int s = 0; s < NP; ++s) {
+            // ---- part A: the block sums
+            // (scalar loads return in any order, so a use waits for ALL that are in flight: this part's constants are
+            //  claimed before the next part's are asked for)
+#pragma unroll
+            for (int k = 0; k < 4 * H; k += 4) TDM_PIN_S(ca[k]);
+            load_b(s, tl, cb);
+            double S0r = ca[0] * sr[0], S1r = ca[1] * sr[0], A0r = ca[2] * dr[0], A1r = ca[3] * dr[0];
+            double S0q = ca[0] * sq[0], S1q = ca[1] * sq[0], A0q = ca[2] * dq[0], A1q = ca[3] * dq[0];
+#pragma unroll
+            for (int j = 1; j < H; ++j) {
+                S0r = fma(ca[4 * j], sr[j], S0r); S1r = fma(ca[4 * j + 1], sr[j], S1r);
+                A0r = fma(ca[4 * j + 2], dr[j], A0r); A1r = fma(ca[4 * j + 3], dr[j], A1r);
+                S0q = fma(ca[4 * j], sq[j], S0q); S1q = fma(ca[4 * j + 1], sq[j], S1q);
+                A0q = fma(ca[4 * j + 2], dq[j], A0q); A1q = fma(ca[4 * j + 3], dq[j], A1q);
+            }
+            // (no fence between the parts, none inside the window's conversions: measured 0.447 against 0.456 ms with them)
+            // ---- part B: outputs at the lane's position Q t, then the two states
+            TDM_PIN_S(cb[0]); TDM_PIN_S(cb[4]);
+            if (tl > 0) { TDM_PIN_S(cb[8]); TDM_PIN_S(cb[12]); }
+            if (s + 1 < NP || t + 1 < NW) load_a((s + 1) % NP, ca);
+            yr[t] = fma(cb[4], vr[s][0], fma(cb[5], vr[s][1], yr[t]));
+            yi[t] = fma(cb[4], vq[s][0], fma(cb[5], vq[s][1], yi[t]));
+            if (tl > 0) {
+                yr[t] = fma(-cb[8], pr[seg][s][0], fma(-cb[9], pr[seg][s][1], yr[t]));
+                yi[t] = fma(-cb[8], pq[seg][s][0], fma(-cb[9], pq[seg][s][1], yi[t]));
+            }
+            {
+                const double m0 = cb[0], m1 = cb[1], m2 = cb[2], m3 = cb[3];
+                const double n0r = fma(m0, vr[s][0], fma(m1, vr[s][1], S0r - A0r)), n1r = fma(m2, vr[s][0], fma(m3, vr[s][1], S1r - A1r));
+                const double n0q = fma(m0, vq[s][0], fma(m1, vq[s][1], S0q - A0q)), n1q = fma(m2, vq[s][0], fma(m3, vq[s][1], S1q - A1q));
+                vr[s][0] = n0r; vr[s][1] = n1r; vq[s][0] = n0q; vq[s][1] = n1q;
+            }
+            const double g0r = S0r + A0r, g1r = S1r + A1r, g0q = S0q + A0q, g1q = S1q + A1q;
+            if (tl == 0) {
+                pr[seg][s][0] = g0r; pr[seg][s][1] = g1r; pq[seg][s][0] = g0q; pq[seg][s][1] = g1q;
+            } else {
+                const double m0 = cb[10], m1 = cb[11], m2 = cb[12], m3 = cb[13];
+                pr[seg][s][0] = fma(m0, g0r, fma(m1, g1r, pr[seg][s][0])); pr[seg][s][1] = fma(m2, g0r, fma(m3, g1r, pr[seg][s][1]));
+                pq[seg][s][0] = fma(m0, g0q, fma(m1, g1q, pq[seg][s][0])); pq[seg][s][1] = fma(m2, g0q, fma(m3, g1q, pq[seg][s][1]));
+            }
+            TDM_PIN(vr[s][0]); TDM_PIN(vr[s][1]); TDM_PIN(vq[s][0]); TDM_PIN(vq[s][1]);
+            TDM_PIN(pr[seg][s][0]); TDM_PIN(pr[seg][s][1]); TDM_PIN(pq[seg][s][0]); TDM_PIN(pq[seg][s][1]);
+            TDM_PIN(yr[t]); TDM_PIN(yi[t]);
+            if (NSEG > 1 && t == SEG - 1) {
+                // (stash is the lane's column of a [16][kWave] array: conflict-free, lane-private, no barrier)
+                stash[(4 * s + 0) * kWave] = pr[0][s][0]; stash[(4 * s + 1) * kWave] = pr[0][s][1];
+                stash[(4 * s + 2) * kWave] = pq[0][s][0]; stash[(4 * s + 3) * kWave] = pq[0][s][1];
+            }
+            TDM_STEP_FENCE();
+        }
+    }
+    // ---- the last output's causal part; the Q - 1 samples past the last window: causal on from v, anticausal from zero
+    double na1[NP], na2[NP];
+#pragma unroll
+    for (int s = 0; s < NP; ++s) {
+        na1[s] = -pz[LY::off_a1 + s];
+        na2[s] = -pz[LY::off_a2 + s];
+        yr[S - 1] = fma(pz[LY::off_b0 + s], vr[s][0], fma(pz[LY::off_b1 + s], vr[s][1], yr[S - 1]));
+        yi[S - 1] = fma(pz[LY::off_b0 + s], vq[s][0], fma(pz[LY::off_b1 + s], vq[s][1], yi[S - 1]));
+        TDM_PIN(yr[S - 1]); TDM_PIN(yi[S - 1]);
+    }
+    TDM_SCHED_FENCE();
+    double a1r[NP], a2r[NP], a1q[NP], a2q[NP];
+#pragma unroll
+    for (int s = 0; s < NP; ++s) { a1r[s] = 0; a2r[s] = 0; a1q[s] = 0; a2q[s] = 0; }
+#pragma unroll
+    for (int k = 0; k < Q - 1; ++k) {
+        pz_raw_cvt<FMT8, false, true>(raw, NW * Q + 1 + k, xfr, xfq);
+        pz_raw_cvt<FMT8, false, true>(raw, L - 1 - k, xbr, xbq);
+#pragma unroll
+        for (int s = 0; s < NP; ++s) {
+            const double wr = fma(na1[s], vr[s][0], fma(na2[s], vr[s][1], xfr)), wq = fma(na1[s], vq[s][0], fma(na2[s], vq[s][1], xfq));
+            vr[s][1] = vr[s][0]; vr[s][0] = wr; vq[s][1] = vq[s][0]; vq[s][0] = wq;
+            const double ar = fma(na1[s], a1r[s], fma(na2[s], a2r[s], xbr)), aq = fma(na1[s], a1q[s], fma(na2[s], a2q[s], xbq));
+            a2r[s] = a1r[s]; a1r[s] = ar; a2q[s] = a1q[s]; a1q[s] = aq;
+        }
+#pragma unroll
+        for (int s = 0; s < NP; ++s) { TDM_PIN(vr[s][0]); TDM_PIN(vq[s][0]); TDM_PIN(a1r[s]); TDM_PIN(a1q[s]); }
+    }
+    TDM_SCHED_FENCE();
+    // ---- the segments' totals chained downwards from u[NW] = (a1, a2); the outputs' share of each segment's start vector
+    pz_raw_cvt<FMT8, false, true>(raw, 0, xfr, xfq);
+#pragma unroll
+    for (int s = 0; s < NP; ++s) {
+        const double *cp = fold + s * LY::kFoldStride;
+        TDM_OPAQUE_SPTR(cp);
+        const auto c = TDM_CPTR(cp);
+        double u0r = a1r[s], u1r = a2r[s], u0q = a1q[s], u1q = a2q[s];
+        yr[S - 1] = fma(c[LY::kfKa], u0r, fma(c[LY::kfKa + 1], u1r, yr[S - 1]));
+        yi[S - 1] = fma(c[LY::kfKa], u0q, fma(c[LY::kfKa + 1], u1q, yi[S - 1]));
+        TDM_PIN(yr[S - 1]); TDM_PIN(yi[S - 1]);
+#pragma unroll
+        for (int seg = NSEG - 1; seg >= 0; --seg) {
+            const int n = (NW - seg * SEG) < SEG ? (NW - seg * SEG) : SEG;
+            const int o = n == SEG ? LY::kfMn : LY::kfSeg + 6 * (n - 1) + 2;
+            const double m0 = c[o], m1 = c[o + 1], m2 = c[o + 2], m3 = c[o + 3];
+            double t0r = pr[seg][s][0], t1r = pr[seg][s][1], t0q = pq[seg][s][0], t1q = pq[seg][s][1];
+            if (NSEG > 1 && seg == 0) {
+                t0r = stash[(4 * s + 0) * kWave]; t1r = stash[(4 * s + 1) * kWave];
+                t0q = stash[(4 * s + 2) * kWave]; t1q = stash[(4 * s + 3) * kWave];
+            }
+            const double n0r = fma(m0, u0r, fma(m1, u1r, t0r)), n1r = fma(m2, u0r, fma(m3, u1r, t1r));
+            const double n0q = fma(m0, u0q, fma(m1, u1q, t0q)), n1q = fma(m2, u0q, fma(m3, u1q, t1q));
+            u0r = n0r; u1r = n1r; u0q = n0q; u1q = n1q;
+#pragma unroll
+            for (int tl = 0; tl < n; ++tl) {
+                const int t = seg * SEG + tl;
+                const int ol = tl == 0 ? LY::kfKa : LY::kfSeg + 6 * (tl - 1);
+                yr[t] = fma(c[ol], u0r, fma(c[ol + 1], u1r, yr[t]));
+                yi[t] = fma(c[ol], u0q, fma(c[ol + 1], u1q, yi[t]));
+                TDM_PIN(yr[t]); TDM_PIN(yi[t]);
+            }
+        }
+        // u[0] = (w'[1], w'[2]): one step to the lane's first sample
+        zr[s][0] = vr[s][0]; zr[s][1] = vr[s][1]; zq[s][0] = vq[s][0]; zq[s][1] = vq[s][1];
+        ur[s][0] = fma(na1[s], u0r, fma(na2[s], u1r, xfr)); ur[s][1] = u0r;
+        uq[s][0] = fma(na1[s], u0q, fma(na2[s], u1q, xfq)); uq[s][1] = u0q;
+    }
+    TDM_SCHED_FENCE();   // (the scans' table loads stay behind the segment totals' last use)
+}
+
+template <int Q, int S, int EDGE, int FMT8, bool WIDE, bool FOLD = true, class Comm>
 TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, Comm &cm, int lane, int blk, int row)
 {
     constexpr int NP = PzLayout::kMaxPairs;
@@ -701,75 +918,79 @@ TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, C
     }
 
     const auto pz = TDM_CPTR(P.pz);
-    const bool inject = (blk == 0 && lane == 0);
-    // the four standing operand pairs of the conversions (pz_raw_perm): forward re / im, backward re / im
-    double xfr, xfq, xbr, xbq;
-    pz_raw_slot_init(xfr); pz_raw_slot_init(xfq); pz_raw_slot_init(xbr); pz_raw_slot_init(xbq);
-    double e0r, e0i;
-    pz_raw_cvt<FMT8, WIDE, true>(raw, G::P0, xfr, xfq);
-    e0r = xfr; e0i = xfq;
     double yr[S], yi[S];
-    {
-        const double dx = pz[PzLayout::off_dx];
+    double zr[NP][2], zq[NP][2], ur[NP][2], uq[NP][2];
+    if constexpr (!WIDE && FOLD && PzRawFold<Q>::value) {
+        pz_raw_fold_lane<Q, S, FMT8>(P, raw, cm.edge_slots() + lane, zr, zq, ur, uq, yr, yi);
+    } else {
+        const bool inject = (blk == 0 && lane == 0);
+        // the four standing operand pairs of the conversions (pz_raw_perm): forward re / im, backward re / im
+        double xfr, xfq, xbr, xbq;
+        pz_raw_slot_init(xfr); pz_raw_slot_init(xfq); pz_raw_slot_init(xbr); pz_raw_slot_init(xbq);
+        double e0r, e0i;
+        pz_raw_cvt<FMT8, WIDE, true>(raw, G::P0, xfr, xfq);
+        e0r = xfr; e0i = xfq;
+        {
+            const double dx = pz[PzLayout::off_dx];
 #pragma unroll
-        for (int t = 0; t < S; ++t) {
-            pz_raw_cvt<FMT8, WIDE, true>(raw, t * Q, xbr, xbq);
-            yr[t] = dx * xbr;
-            yi[t] = dx * xbq;
-        }
-    }
-    // ---------------- phase 1: all pole pairs per sample (a sample is converted once per direction) ----------------
-    double na1[NP], na2[NP], b0[NP], b1[NP];
-#pragma unroll
-    for (int s = 0; s < NP; ++s) {
-        na1[s] = -pz[PzLayout::off_a1 + s];
-        na2[s] = -pz[PzLayout::off_a2 + s];
-        b0[s] = pz[PzLayout::off_b0 + s];
-        b1[s] = pz[PzLayout::off_b1 + s];
-    }
-    double f1r[NP], f2r[NP], f1q[NP], f2q[NP], a1r[NP], a2r[NP], a1q[NP], a2q[NP];
-#pragma unroll
-    for (int s = 0; s < NP; ++s) { f1r[s] = 0; f2r[s] = 0; f1q[s] = 0; f2q[s] = 0; a1r[s] = 0; a2r[s] = 0; a1q[s] = 0; a2q[s] = 0; }
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-        const int ib = L - 1 - i;
-        if (i == G::P0) {
-            // scipy's zi*ext[0]: constant history ext[0] before the first extended sample
-#pragma unroll
-            for (int s = 0; s < NP; ++s) {
-                const double g = pz[PzLayout::off_g + s];
-                f1r[s] = inject ? g * e0r : f1r[s]; f2r[s] = inject ? g * e0r : f2r[s];
-                f1q[s] = inject ? g * e0i : f1q[s]; f2q[s] = inject ? g * e0i : f2q[s];
+            for (int t = 0; t < S; ++t) {
+                pz_raw_cvt<FMT8, WIDE, true>(raw, t * Q, xbr, xbq);
+                yr[t] = dx * xbr;
+                yi[t] = dx * xbq;
             }
         }
-        pz_raw_cvt<FMT8, WIDE, true>(raw, i, xfr, xfq);
-        pz_raw_cvt<FMT8, WIDE, true>(raw, ib, xbr, xbq);
+        // ---------------- phase 1: all pole pairs per sample (a sample is converted once per direction) ----------------
+        double na1[NP], na2[NP], b0[NP], b1[NP];
 #pragma unroll
         for (int s = 0; s < NP; ++s) {
-            const double wr = fma(na1[s], f1r[s], fma(na2[s], f2r[s], xfr)), wq = fma(na1[s], f1q[s], fma(na2[s], f2q[s], xfq));
-            if (i % Q == 0) {
-                yr[i / Q] = fma(b0[s], wr, fma(b1[s], f1r[s], yr[i / Q]));
-                yi[i / Q] = fma(b0[s], wq, fma(b1[s], f1q[s], yi[i / Q]));
-            }
-            f2r[s] = f1r[s]; f1r[s] = wr; f2q[s] = f1q[s]; f1q[s] = wq;
-            const double vr = fma(na1[s], a1r[s], fma(na2[s], a2r[s], xbr)), vq = fma(na1[s], a1q[s], fma(na2[s], a2q[s], xbq));
-            if (ib % Q == 0) {
-                yr[ib / Q] = fma(b0[s], vr, fma(b1[s], a1r[s], yr[ib / Q]));
-                yi[ib / Q] = fma(b0[s], vq, fma(b1[s], a1q[s], yi[ib / Q]));
-            }
-            a2r[s] = a1r[s]; a1r[s] = vr; a2q[s] = a1q[s]; a1q[s] = vq;
+            na1[s] = -pz[PzLayout::off_a1 + s];
+            na2[s] = -pz[PzLayout::off_a2 + s];
+            b0[s] = pz[PzLayout::off_b0 + s];
+            b1[s] = pz[PzLayout::off_b1 + s];
         }
-        // one sample step at a time (see TDM_PIN): keeps conversions and chains of later steps from being hoisted
+        double f1r[NP], f2r[NP], f1q[NP], f2q[NP], a1r[NP], a2r[NP], a1q[NP], a2q[NP];
 #pragma unroll
-        for (int s = 0; s < NP; ++s) { TDM_PIN(f1r[s]); TDM_PIN(f1q[s]); TDM_PIN(a1r[s]); TDM_PIN(a1q[s]); }
-        if (i % Q == 0) { TDM_PIN(yr[i / Q]); TDM_PIN(yi[i / Q]); }
-        if (ib % Q == 0) { TDM_PIN(yr[ib / Q]); TDM_PIN(yi[ib / Q]); }
-    }
-    double zr[NP][2], zq[NP][2], ur[NP][2], uq[NP][2];
+        for (int s = 0; s < NP; ++s) { f1r[s] = 0; f2r[s] = 0; f1q[s] = 0; f2q[s] = 0; a1r[s] = 0; a2r[s] = 0; a1q[s] = 0; a2q[s] = 0; }
 #pragma unroll
-    for (int s = 0; s < NP; ++s) {
-        zr[s][0] = f1r[s]; zr[s][1] = f2r[s]; zq[s][0] = f1q[s]; zq[s][1] = f2q[s];
-        ur[s][0] = a1r[s]; ur[s][1] = a2r[s]; uq[s][0] = a1q[s]; uq[s][1] = a2q[s];
+        for (int i = 0; i < L; ++i) {
+            const int ib = L - 1 - i;
+            if (i == G::P0) {
+                // scipy's zi*ext[0]: constant history ext[0] before the first extended sample
+#pragma unroll
+                for (int s = 0; s < NP; ++s) {
+                    const double g = pz[PzLayout::off_g + s];
+                    f1r[s] = inject ? g * e0r : f1r[s]; f2r[s] = inject ? g * e0r : f2r[s];
+                    f1q[s] = inject ? g * e0i : f1q[s]; f2q[s] = inject ? g * e0i : f2q[s];
+                }
+            }
+            pz_raw_cvt<FMT8, WIDE, true>(raw, i, xfr, xfq);
+            pz_raw_cvt<FMT8, WIDE, true>(raw, ib, xbr, xbq);
+#pragma unroll
+            for (int s = 0; s < NP; ++s) {
+                const double wr = fma(na1[s], f1r[s], fma(na2[s], f2r[s], xfr)), wq = fma(na1[s], f1q[s], fma(na2[s], f2q[s], xfq));
+                if (i % Q == 0) {
+                    yr[i / Q] = fma(b0[s], wr, fma(b1[s], f1r[s], yr[i / Q]));
+                    yi[i / Q] = fma(b0[s], wq, fma(b1[s], f1q[s], yi[i / Q]));
+                }
+                f2r[s] = f1r[s]; f1r[s] = wr; f2q[s] = f1q[s]; f1q[s] = wq;
+                const double vr = fma(na1[s], a1r[s], fma(na2[s], a2r[s], xbr)), vq = fma(na1[s], a1q[s], fma(na2[s], a2q[s], xbq));
+                if (ib % Q == 0) {
+                    yr[ib / Q] = fma(b0[s], vr, fma(b1[s], a1r[s], yr[ib / Q]));
+                    yi[ib / Q] = fma(b0[s], vq, fma(b1[s], a1q[s], yi[ib / Q]));
+                }
+                a2r[s] = a1r[s]; a1r[s] = vr; a2q[s] = a1q[s]; a1q[s] = vq;
+            }
+            // one sample step at a time (see TDM_PIN): keeps conversions and chains of later steps from being hoisted
+#pragma unroll
+            for (int s = 0; s < NP; ++s) { TDM_PIN(f1r[s]); TDM_PIN(f1q[s]); TDM_PIN(a1r[s]); TDM_PIN(a1q[s]); }
+            if (i % Q == 0) { TDM_PIN(yr[i / Q]); TDM_PIN(yi[i / Q]); }
+            if (ib % Q == 0) { TDM_PIN(yr[ib / Q]); TDM_PIN(yi[ib / Q]); }
+        }
+#pragma unroll
+        for (int s = 0; s < NP; ++s) {
+            zr[s][0] = f1r[s]; zr[s][1] = f2r[s]; zq[s][0] = f1q[s]; zq[s][1] = f2q[s];
+            ur[s][0] = a1r[s]; ur[s][1] = a2r[s]; uq[s][0] = a1q[s]; uq[s][1] = a2q[s];
+        }
     }
     pz_block_finish<Q, S, EDGE>(P, cm, lane, blk, row, zr, zq, ur, uq, yr, yi, pz[PzLayout::off_yc]);
     // the last extended sample, as an integer: 2 u[n-1] - u[n-1-edge]

@@ -44,7 +44,21 @@ struct PzLayout {
     TDM_HD static int off_AE(int S) { return off_AG(S) + kMaxD * kMaxD; }        // [D][D] V <- exported lane state of the last block
     TDM_HD static int off_wx(int S) { return off_AE(S) + kMaxD * kMaxD; }        // [D]    V <- ext[last]
     TDM_HD static int off_rowm(int S) { return off_wx(S) + kMaxD; }              // [16][NP][4] C^(L (r+1)), r = position in a 16-lane row
-    TDM_HD static int size(int S) { return off_rowm(S) + 16 * kMaxPairs * 4; }
+    // folded block-sum form of the raw-integer kernel's narrow blocks (pz_raw_fold_lane, out_stride == kFoldQ; zero
+    // otherwise).  Per pair kFoldStride doubles, M = C^Q, gamma_j = (h_j, h_{j-1}), h the all-pole impulse response:
+    //   [4 j + 0..3], j < kFoldH : (gamma_j + gamma_{Q-1-j}) / 2 and (gamma_j - gamma_{Q-1-j}) / 2, two components each
+    //   [kfM + 0..3]             : M
+    //   [kfKc + 0..1]            : causal output taps (b0, b1) on (w[n], w[n-1])
+    //   [kfKa + 0..1]            : anticausal output taps (b1 - b0 a1, -b0 a2) on (w'[n+1], w'[n+2])
+    //   [kfSeg + 6 (t - 1) + 0..5], 1 <= t < kFoldSeg : kfKa^T M^-t (2), M^t (4) -- window t of a segment
+    //   [kfMn + 0..3]            : M^kFoldSeg
+    // then one double: the direct term plus sum b0 (the x[n] part of the anticausal outputs).
+    static constexpr int kFoldQ = 10, kFoldH = kFoldQ / 2, kFoldSeg = 4;
+    static constexpr int kfM = 4 * kFoldH, kfKc = kfM + 4, kfKa = kfKc + 2, kfSeg = kfKa + 2, kfMn = kfSeg + 6 * (kFoldSeg - 1);
+    static constexpr int kFoldStride = kfMn + 4;
+    TDM_HD static int off_fold(int S) { return off_rowm(S) + 16 * kMaxPairs * 4; }
+    TDM_HD static int off_fold_dx(int S) { return off_fold(S) + kMaxPairs * kFoldStride; }
+    TDM_HD static int size(int S) { return off_fold_dx(S) + 2; }
 };
 
 namespace detail {
@@ -290,6 +304,43 @@ inline std::shared_ptr<const PzShared> build_pz_shared(const double (*sos)[6], i
         pz[PzLayout::off_g + s] = (double)(1 / (1 + a1[s] + a2[s]));
     }
     pz[PzLayout::off_dx] = (double)dz.dx;
+    if (qs == PzLayout::kFoldQ && S > 0) {
+        // ---- folded block sums (PzLayout::off_fold): both banks of a pair from one sum over a window of Q samples
+        constexpr int FQ = PzLayout::kFoldQ, FH = PzLayout::kFoldH;
+        ldbl b0sum = 0;
+        for (int s = 0; s < NP; ++s) {
+            double *o = &pz[PzLayout::off_fold(S) + (size_t)s * PzLayout::kFoldStride];
+            ldbl hh[FQ + 1];   // hh[j + 1] = h_j, hh[0] = h_{-1} = 0
+            hh[0] = 0;
+            hh[1] = 1;
+            for (int j = 1; j < FQ; ++j) hh[j + 1] = -a1[s] * hh[j] - a2[s] * hh[j - 1];
+            for (int j = 0; j < FH; ++j) {
+                const int k = FQ - 1 - j;
+                o[4 * j + 0] = (double)((hh[j + 1] + hh[k + 1]) / 2);
+                o[4 * j + 1] = (double)((hh[j] + hh[k]) / 2);
+                o[4 * j + 2] = (double)((hh[j + 1] - hh[k + 1]) / 2);
+                o[4 * j + 3] = (double)((hh[j] - hh[k]) / 2);
+            }
+            const M2 m = m2pow(C[s], FQ), mi = m2inv(m);
+            auto put = [](double *d, const M2 &x) { d[0] = (double)x.a; d[1] = (double)x.b; d[2] = (double)x.c; d[3] = (double)x.d; };
+            put(o + PzLayout::kfM, m);
+            o[PzLayout::kfKc] = (double)b0[s];
+            o[PzLayout::kfKc + 1] = (double)b1[s];
+            const ldbl ka0 = b1[s] - b0[s] * a1[s], ka1 = -b0[s] * a2[s];
+            o[PzLayout::kfKa] = (double)ka0;
+            o[PzLayout::kfKa + 1] = (double)ka1;
+            for (int tt = 1; tt < PzLayout::kFoldSeg; ++tt) {
+                const M2 mt = m2pow(m, tt), it = m2pow(mi, tt);
+                double *e = o + PzLayout::kfSeg + 6 * (tt - 1);
+                e[0] = (double)(ka0 * it.a + ka1 * it.c);
+                e[1] = (double)(ka0 * it.b + ka1 * it.d);
+                put(e + 2, mt);
+            }
+            put(o + PzLayout::kfMn, m2pow(m, PzLayout::kFoldSeg));
+            b0sum += b0[s];
+        }
+        pz[PzLayout::off_fold_dx(S)] = (double)(dz.dx + b0sum);
+    }
     pz[PzLayout::off_yc] = (double)(((ldbl)in_offset + (ldbl)in_scale * (ldbl)in_bias) * h.h1 * h.h1);
     for (int r = 0; r < D; ++r) pz[PzLayout::off_wx(S) + r] = (double)dz.AE[(size_t)r * (D + 1) + D];
     pz_fill_carry_tables(h, (int)Bn, 0, R_reg, &blob[h.off_T1reg], &blob[h.off_T2reg]);   // the full blocks' carry tables

@@ -53,6 +53,7 @@ struct DebugSwitch { const char *key; std::atomic<long long> value; long long df
 static DebugSwitch g_debug[] = {
     {"no_raw", {0}, 0},                  // 1: cu8 plans made from now on never take the raw-integer decimator
     {"raw_min_blocks", {-1}, -1},        // >= 0: blocks below which a batch stays on the double-based decimator (plans made from now on)
+    {"raw_fold", {1}, 1},                // 0: plans made from now on run the raw-integer decimator's narrow blocks sample by sample (q = 10)
     {"gardner_fused", {1}, 1},           // 0: Gardner mode as three launches (matched filter -> HBM -> loop -> decisions)
     {"pfb_direct", {0}, 0},              // 1: channeliser plans made from now on use the direct-DFT kernel
     {"pfb_rounds", {0}, 0},              // > 0: rounds per channeliser workgroup (plans made from now on)
@@ -268,6 +269,7 @@ struct HipBackend {
     StageTimer *timer = nullptr;
     hipError_t err = hipSuccess;
     int device = 0;
+    bool raw_fold = true;   // tdm_debug_set "raw_fold" as the plan saw it
 
     struct Scope {
         HipBackend &be; int stage; Event a, b; bool on;
@@ -299,7 +301,7 @@ struct HipBackend {
     void pz_raw(const ZpParams &P, const void *iq, int64_t stride, int b_tail, int rows)
     {
         Scope s(*this, ST_DEC_BLOCK);
-        launch_pz_raw<Q, S, EDGE, FMT8>(P, iq, stride, b_tail, rows, stream);
+        launch_pz_raw<Q, S, EDGE, FMT8>(P, iq, stride, b_tail, rows, raw_fold, stream);
     }
     template <class Src>
     void lp2(const Lp2Params &P, const Src &src, int rows)
@@ -427,6 +429,7 @@ struct tdm_plan {
     int32_t fast_pre_shift = 0;   // tdm_plan_option "fast_pre_shift"
     int32_t rows_per_chunk = 1;   // tdm_plan_option "rows_per_chunk"
     int64_t raw_min_blocks = 0;
+    bool raw_fold = true;         // tdm_debug_set "raw_fold" when the plan was made
     std::map<int64_t, std::unique_ptr<Variant>> variants;
     Variant *cur = nullptr;
     uint64_t clock = 0;
@@ -882,6 +885,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
     }
     // (tdm_debug_set("no_raw", 1): experiments / tests keep cu8 plans on the kernel that holds its samples as doubles)
     p->allow_raw = debug_value("no_raw") != 1;
+    p->raw_fold = debug_value("raw_fold") != 0;
     {
         // blocks of the double-based decimator below which a batch stays on it: two wavefronts per SIMD of the device
         // (tdm_debug_set("raw_min_blocks", n) overrides; tests use 0 to put single carriers on the raw-integer kernel)
@@ -1005,6 +1009,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
     be.stream = stream ? (hipStream_t)stream : plan->stream.get();
     be.timer = &plan->timer;
     be.device = plan->device;
+    be.raw_fold = plan->raw_fold;
     if (plan->mode == TDM_MODE_TETRA || plan->mode == TDM_MODE_TETRA_GARDNER) {
         if (pre_shift_hz || freq_offset_hz)
             return fail(TDM_ERR_UNSUPPORTED, "TETRA mode: carrier offsets are estimated, not supplied");
