@@ -93,7 +93,8 @@ typedef struct tdm_plan_info {
     int32_t mode;
     int32_t device;
     int32_t dec_engine;   /* decimator kernel the next call runs: 0 none, 1 cascade engine, 2 parallel form on doubles,
-                             3 parallel form on the raw bytes (cu8 batches of at least 8 blocks per CU) */
+                             3 parallel form on the raw bytes (cu8 batches of at least 8 blocks per CU; never a plan with
+                             rows_per_chunk > 1) */
     int32_t gardner_segments; /* TDM_MODE_TETRA_GARDNER: the number of independently started loops every carrier's chunk is
                              walked as, joined at seams: by default the largest of 2, 4, 8 that leaves every loop its 384
                              warm-up symbols -- a function of the chunk (length, rate, taps) alone, never of the batch --

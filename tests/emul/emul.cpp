@@ -373,6 +373,22 @@ int emu_process(double sample_rate, int64_t n, int rows, int fmt, const void *iq
     return 0;
 }
 
+// what tdm_plan_get_info reports as dec_engine for a plan of this rate, length, wire format and row count as emu_process
+// runs it (the rule of run_ref_fmt for a call without a pre-shift; this emulation's raw_min_blocks is 0): 0 not decimated,
+// 1 cascade, 2 parallel form on doubles, 3 raw bytes.  geom (or null), engine 3 only: the raw-byte decimator's launch --
+// {lane length, blocks, first tail block (run_pz_raw's b_tail), decimated length}
+int emu_dec_engine(double sample_rate, int64_t n, int fmt, int rows, int64_t *geom)
+{
+    RefPlanHost h = build_ref_plan(sample_rate, n, 25000.0, g_allow_pz, g_allow_raw ? fmt : -1);
+    if (!h.decimated) return 0;
+    const bool raw = h.raw_S > 0 && fmt == FMT_CU8 && g_rows_per_chunk <= 1 && (int64_t)rows * h.dec.p.nb >= h.raw_min_blocks;
+    if (raw && geom) {
+        const ZpParams &p = h.dec_raw.p;
+        geom[0] = p.L; geom[1] = p.nb; geom[2] = pz_raw_first_tail_block(p); geom[3] = h.n_dec;
+    }
+    return raw ? 3 : (h.pz_S ? 2 : 1);
+}
+
 // one zero-phase stage on c128 data: kind 0 = decimator sos (q), kind 1 = butter tf (bandwidth, fs)
 int emu_zp_stage(int kind, const double *x, int64_t n, int q, double bandwidth, double fs, double *y)
 {

@@ -44,6 +44,19 @@ def process(sample_rate, iq, fmt, n, rows=1, stride=None, pre_shift=None, freq_o
     return hard, soft, n_soft, bp, mm
 
 
+def dec_engine(sample_rate, n, fmt="cu8", rows=1, rows_per_chunk=1):
+    """(engine, geometry): what tdm_plan_get_info would report as dec_engine for the plan `process` runs for these
+    arguments (3 = the raw-byte decimator), and for engine 3 the raw-byte launch as a dict: lane length L, blocks nb,
+    first tail block b_tail (blocks 1 .. b_tail - 1 are the narrow ones, b_tail .. nb - 1 hold the tail extension),
+    decimated length n_dec; None for the other engines."""
+    L = lib()
+    L.emu_rows_per_chunk(int(rows_per_chunk))
+    g = (C.c_int64 * 4)()
+    e = L.emu_dec_engine(C.c_double(sample_rate), C.c_int64(n), FMT[fmt], int(rows), g)
+    L.emu_rows_per_chunk(1)
+    return e, (dict(L=g[0], nb=g[1], b_tail=g[2], n_dec=g[3]) if e == 3 else None)
+
+
 class fast_pre_shift:
     """`with emul.fast_pre_shift(): ...` -- the plan option of the same name (the input-rate shift's phase as the ideal ramp)"""
 

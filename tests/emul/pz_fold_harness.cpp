@@ -36,9 +36,7 @@ int run_one(double sample_rate, int64_t n, const void *iq, double freq_offset, d
     if (!h.lp2.ok || !h.raw_S) return -1;   // (this length / rate does not take the raw-integer decimator)
     {
         const ZpParams &p = h.dec_raw.p;
-        int b_tail = (int)((p.k0L + p.n) / (kWave * p.L));
-        if (b_tail > p.nb - 1) b_tail = p.nb - 1;
-        if (narrow_blocks) *narrow_blocks = b_tail - 1;
+        if (narrow_blocks) *narrow_blocks = pz_raw_first_tail_block(p) - 1;
     }
     if (!iq) return 0;
     HostZp dec, dec_raw;

@@ -78,6 +78,7 @@ class BatchDemodulator:
         """tdm_plan_option "rows_per_chunk": the plan's rows are T x c -- c carriers out of each of T consecutive chunks of one
         stream (rows r c ... r c + c - 1 read input row r); pre-shifts and offsets stay per plan row."""
         check(self.lib.tdm_plan_option(self.handle, b"rows_per_chunk", int(c)))
+        check(self.lib.tdm_plan_get_info(self.handle, C.byref(self.info)))   # (dec_engine: such a plan never takes the raw-byte kernel)
         self.rows_per_chunk = int(c)
         return self
 

@@ -62,12 +62,19 @@ void run_pz_block(BE &be, const RefPlanHost &h, const ZpParams &P, const RawLoad
 
 // raw-integer decimator (cu8): blocks that hold no extension sample run on the bytes as they are, the first block and
 // the block(s) with the tail extension (from b_tail on) on int16 pairs
-template <class BE>
-void run_pz_raw(BE &be, const RefPlanHost &h, const ZpParams &P, const void *iq, int64_t stride, int rows)
+// (one function: the launch below and the tests' geometry query, tests/emul, have to agree on it)
+inline int pz_raw_first_tail_block(const ZpParams &P)
 {
     const int nb = P.nb, Bn = kWave * P.L;
     int b_tail = (int)((P.k0L + P.n) / Bn);   // block of the first position past the signal
     if (b_tail > nb - 1) b_tail = nb - 1;
+    return b_tail;
+}
+
+template <class BE>
+void run_pz_raw(BE &be, const RefPlanHost &h, const ZpParams &P, const void *iq, int64_t stride, int rows)
+{
+    const int b_tail = pz_raw_first_tail_block(P);
     switch (h.q) {
 #define TDM_PZR_CASE(Q, S) case Q: be.template pz_raw<Q, S, kEdgeSos, FMT_CU8>(P, iq, stride, b_tail, rows); break;
         TDM_PZR_CASES(TDM_PZR_CASE)

@@ -989,8 +989,9 @@ int tdm_plan_get_info(const tdm_plan *plan, tdm_plan_info *info)
     //  walk whole chunks)
     info->gardner_segments = plan->mode == TDM_MODE_TETRA_GARDNER ? ((debug_value("gardner_fused") != 0 && plan->gardner_fused_ok) ? plan->gardner_seg : 1) : 0;
     if (plan->mode == TDM_MODE_REFERENCE && h.decimated) {
-        // (the rule of run_ref_fmt; a call with an input-rate pre-shift stays on the double-based kernel)
-        const bool raw = h.raw_S > 0 && plan->fmt == TDM_CU8 && (int64_t)plan->rows * h.dec.p.nb >= h.raw_min_blocks;
+        // (the rule of run_ref_fmt; a call with an input-rate pre-shift stays on the double-based kernel, and so does every
+        //  call of a plan whose rows share input rows)
+        const bool raw = h.raw_S > 0 && plan->fmt == TDM_CU8 && plan->rows_per_chunk <= 1 && (int64_t)plan->rows * h.dec.p.nb >= h.raw_min_blocks;
         info->dec_engine = raw ? 3 : (h.pz_S ? 2 : 1);
     }
     return TDM_OK;
