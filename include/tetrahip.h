@@ -117,6 +117,9 @@ TDM_API int tdm_last_error(char *buf, size_t buflen);
  *   "raw_fold"        0: the raw-byte decimator of plans created from now on steps its filters through every sample of
  *                     the interior blocks instead of through folded sums over windows of q samples (q = 10; equal
  *                     decisions, soft symbols within the arithmetic's rounding of each other)               (default 1)
+ *   "raw_edge_fill"   0: the raw-byte decimator's first and tail blocks have each lane that holds extension or pad samples
+ *                     fetch them itself, one at a time, instead of the whole wavefront building them together.  Read at
+ *                     every tdm_process* call, not when the plan is made; equal results bit for bit           (default 1)
  *   "gardner_fused"   0: TDM_MODE_TETRA_GARDNER as three launches (matched filter -> HBM -> loop -> decisions)  (default 1)
  *   "gardner_segments" what tdm_plan_option "gardner_segments" sets per plan, for TDM_MODE_TETRA_GARDNER plans created from
  *                     now on: 0 whole chunks, 1 the default, K > 1 at most K pieces, -1 fitted to the batch   (default 1)

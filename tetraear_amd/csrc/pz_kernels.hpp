@@ -520,7 +520,8 @@ TDM_HD void pz_block_body(const ZpParams &P, const Loader &ld, Comm &cm, int lan
 // Each sample is converted once per direction (cheap: byte -> f32 -> f64).
 //   WIDE = false : interior blocks, two samples per dword as they come off the wire
 //   WIDE = true  : the first block and the block(s) holding the tail extension: samples as int16 pairs, because the odd
-//                  extension 2 u[0] - u[k] does not fit a byte; extension lanes are filled through a small LDS buffer
+//                  extension 2 u[0] - u[k] does not fit a byte; the lanes holding extension or pad samples read theirs from a
+//                  small LDS buffer that the whole wavefront fills (pz_raw_fill_edges)
 // ------------------------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TDM_OPAQUE_V(x) asm volatile("" : "+v"(x))
@@ -837,6 +838,73 @@ TDM_HD void pz_raw_fold_lane(const ZpParams &P, const uint32_t *raw, double *sta
     TDM_SCHED_FENCE();   // (the scans' table loads stay behind the segment totals' last use)
 }
 
+// the two bytes of sample k as one word (re in the low byte), and the integers in it
+TDM_HD uint32_t pz_raw_pair(const void *rowp, int64_t k)
+{
+    const uint8_t *p = (const uint8_t *)rowp + 2 * k;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+}
+template <int FMT8>
+TDM_HD void pz_raw_unpair(uint32_t w, int &re, int &im)
+{
+    re = FMT8 == FMT_CU8 ? (int)(w & 0xffu) : (int)(int8_t)(w & 0xffu);
+    im = FMT8 == FMT_CU8 ? (int)((w >> 8) & 0xffu) : (int)(int8_t)((w >> 8) & 0xffu);
+}
+
+// ------------------------------------------------------------------------------------------
+// The edge slots of a wide block, built by the whole wavefront.  A wide block has at most kSlots lanes that hold samples of
+// the odd extension or positions past the extended row (PzEdgeGeom): the first kHead lanes of block 0 and the kTail lanes
+// from the one with the signal's last sample on, which may straddle two blocks.  Their kSlots * L int16 pairs are
+// elements j = slot * L + i of Comm::edge_slots(); every lane takes the elements lane, lane + 64, ... (a fully unrolled share
+// of ceil(kSlots L / 64)), reads the two anchors u[0] and u[n-1] once, issues the loads of all its elements, and writes its
+// share in one pass.  The integers are those of the per-lane loop in pz_raw_body (2 u[0] - u[EDGE - e], the row's own
+// samples, 2 u[n-1] - u[n-2-(e-EDGE-n)]; PzRawBias inside the extended row, true zero outside it).  An element outside
+// the extended row, or of a slot whose lane belongs to another block, issues no load; the latter is not written either.
+// The caller's wave_sync() stands between this and the edge lanes' reads.
+// ------------------------------------------------------------------------------------------
+template <int L, int EDGE, int FMT8, class Comm>
+TDM_HD void pz_raw_fill_edges(Comm &cm, const char *rowp, int64_t n, int blk, int lane)
+{
+    typedef PzEdgeGeom<L, EDGE> G;
+    constexpr int N = G::kSlots * L, PER = (N + kWave - 1) / kWave;
+    const int64_t blk0 = (int64_t)blk * (kWave * L);
+    const int64_t seg_t0 = ((G::P0 + EDGE + n) / L) * L;   // first position of the lane with the signal's last sample
+    uint32_t *buf = (uint32_t *)cm.edge_slots();
+    uint32_t wa0 = pz_raw_pair(rowp, 0), wa1 = pz_raw_pair(rowp, n - 1);
+    uint32_t w[PER];
+    bool mine[PER];
+    int kind[PER];   // 0: outside the extended row, 1: head extension, 2: the row itself, 3: tail extension
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int j = lane + k * kWave;
+        const int slot = j / L, i = j - slot * L;
+        const int64_t seg = slot < G::kHead ? (int64_t)slot * L : seg_t0 + (int64_t)(slot - G::kHead) * L;
+        const int64_t e = seg - G::P0 + i, d = e - EDGE;   // d: the position counted from the row's first sample
+        mine[k] = j < N && seg >= blk0 && seg < blk0 + kWave * L;
+        kind[k] = (!mine[k] || e < 0 || e >= n + 2 * (int64_t)EDGE) ? 0 : (d < 0 ? 1 : (d < n ? 2 : 3));
+        // the sample read is the position mirrored at the row's end it lies beyond: EDGE - e, e - EDGE, n - 2 - (e - EDGE - n)
+        w[k] = 0;
+        if (kind[k]) w[k] = pz_raw_pair(rowp, d < 0 ? -d : (d < n ? d : 2 * (n - 1) - d));
+    }
+    // (every load above is in flight before the first of them is waited for: the words are first looked at from here on)
+    TDM_OPAQUE_V(wa0);
+    TDM_OPAQUE_V(wa1);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) TDM_OPAQUE_V(w[k]);
+    int a0r, a0i, a1r, a1i;
+    pz_raw_unpair<FMT8>(wa0, a0r, a0i);
+    pz_raw_unpair<FMT8>(wa1, a1r, a1i);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        int vr, vi;
+        pz_raw_unpair<FMT8>(w[k], vr, vi);
+        if (kind[k] == 1) { vr = 2 * a0r - vr; vi = 2 * a0i - vi; }
+        if (kind[k] == 3) { vr = 2 * a1r - vr; vi = 2 * a1i - vi; }
+        if (kind[k]) { vr += PzRawBias<FMT8>::value; vi += PzRawBias<FMT8>::value; }   // (2 (a + B) - (b + B) = 2 a - b + B)
+        if (mine[k]) buf[lane + k * kWave] = kind[k] ? ((uint32_t)vr & 0xffffu) | ((uint32_t)vi << 16) : 0u;
+    }
+}
+
 template <int Q, int S, int EDGE, int FMT8, bool WIDE, bool FOLD = true, class Comm>
 TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, Comm &cm, int lane, int blk, int row)
 {
@@ -850,6 +918,13 @@ TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, C
     const int64_t e0 = seg - G::P0;   // ext index of the lane's first sample
     const char *rowp = (const char *)iq + (int64_t)row * row_stride * 2;
     uint32_t raw[NR];
+    if constexpr (WIDE) {
+        // (a wavefront-uniform choice, made before the lanes part ways: every lane reaches the one wave_sync)
+        if (!P.raw_edge_loop) {
+            pz_raw_fill_edges<L, EDGE, FMT8>(cm, rowp, n, blk, lane);
+            cm.wave_sync();
+        }
+    }
     if (e0 >= EDGE && e0 + L <= EDGE + n) {
         const char *p = rowp + (e0 - EDGE) * 2;
         uint32_t w[L / 2];
@@ -888,30 +963,34 @@ TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, C
             slot = G::kHead + (int)((seg - seg_t0) / L);
         }
         uint32_t *buf = (uint32_t *)cm.edge_slots() + (size_t)slot * L;
+        // ZpParams::raw_edge_loop (tdm_debug_set "raw_edge_fill" 0): the lane builds its slot itself, sample by sample --
+        // what pz_raw_fill_edges replaced, kept as its A/B partner
+        if (P.raw_edge_loop) {
 #pragma unroll 1
-        for (int i = 0; i < L; ++i) {
-            const int64_t e = e0 + i;
-            int re = 0, im = 0;
-            if (e >= 0 && e < n + 2 * (int64_t)EDGE) {
-                if (e < EDGE) {  // 2*x[0] - x[edge - e]
-                    int ar, ai;
-                    pz_raw_sample<FMT8>(rowp, 0, ar, ai);
-                    pz_raw_sample<FMT8>(rowp, EDGE - e, re, im);
-                    re = 2 * ar - re;
-                    im = 2 * ai - im;
-                } else if (e < EDGE + n) {
-                    pz_raw_sample<FMT8>(rowp, e - EDGE, re, im);
-                } else {  // 2*x[n-1] - x[n-2-(e-edge-n)]
-                    int ar, ai;
-                    pz_raw_sample<FMT8>(rowp, n - 1, ar, ai);
-                    pz_raw_sample<FMT8>(rowp, n - 2 - (e - EDGE - n), re, im);
-                    re = 2 * ar - re;
-                    im = 2 * ai - im;
+            for (int i = 0; i < L; ++i) {
+                const int64_t e = e0 + i;
+                int re = 0, im = 0;
+                if (e >= 0 && e < n + 2 * (int64_t)EDGE) {
+                    if (e < EDGE) {  // 2*x[0] - x[edge - e]
+                        int ar, ai;
+                        pz_raw_sample<FMT8>(rowp, 0, ar, ai);
+                        pz_raw_sample<FMT8>(rowp, EDGE - e, re, im);
+                        re = 2 * ar - re;
+                        im = 2 * ai - im;
+                    } else if (e < EDGE + n) {
+                        pz_raw_sample<FMT8>(rowp, e - EDGE, re, im);
+                    } else {  // 2*x[n-1] - x[n-2-(e-edge-n)]
+                        int ar, ai;
+                        pz_raw_sample<FMT8>(rowp, n - 1, ar, ai);
+                        pz_raw_sample<FMT8>(rowp, n - 2 - (e - EDGE - n), re, im);
+                        re = 2 * ar - re;
+                        im = 2 * ai - im;
+                    }
+                    re += PzRawBias<FMT8>::value;   // (2 (a + B) - (b + B) = 2 a - b + B: the extension of the biased row)
+                    im += PzRawBias<FMT8>::value;
                 }
-                re += PzRawBias<FMT8>::value;   // (2 (a + B) - (b + B) = 2 a - b + B: the extension of the biased row)
-                im += PzRawBias<FMT8>::value;
+                buf[i] = ((uint32_t)re & 0xffffu) | ((uint32_t)im << 16);
             }
-            buf[i] = ((uint32_t)re & 0xffffu) | ((uint32_t)im << 16);
         }
 #pragma unroll
         for (int i = 0; i < NR; ++i) raw[i] = buf[i];

@@ -54,6 +54,7 @@ static DebugSwitch g_debug[] = {
     {"no_raw", {0}, 0},                  // 1: cu8 plans made from now on never take the raw-integer decimator
     {"raw_min_blocks", {-1}, -1},        // >= 0: blocks below which a batch stays on the double-based decimator (plans made from now on)
     {"raw_fold", {1}, 1},                // 0: plans made from now on run the raw-integer decimator's narrow blocks sample by sample (q = 10)
+    {"raw_edge_fill", {1}, 1},           // 0: the raw-integer decimator's wide blocks fill their edge lanes lane by lane (read at every call)
     {"gardner_fused", {1}, 1},           // 0: Gardner mode as three launches (matched filter -> HBM -> loop -> decisions)
     {"pfb_direct", {0}, 0},              // 1: channeliser plans made from now on use the direct-DFT kernel
     {"pfb_rounds", {0}, 0},              // > 0: rounds per channeliser workgroup (plans made from now on)
@@ -270,6 +271,7 @@ struct HipBackend {
     hipError_t err = hipSuccess;
     int device = 0;
     bool raw_fold = true;   // tdm_debug_set "raw_fold" as the plan saw it
+    bool raw_edge_loop = false;   // tdm_debug_set "raw_edge_fill" 0 as this call saw it (ZpParams::raw_edge_loop)
 
     struct Scope {
         HipBackend &be; int stage; Event a, b; bool on;
@@ -301,7 +303,9 @@ struct HipBackend {
     void pz_raw(const ZpParams &P, const void *iq, int64_t stride, int b_tail, int rows)
     {
         Scope s(*this, ST_DEC_BLOCK);
-        launch_pz_raw<Q, S, EDGE, FMT8>(P, iq, stride, b_tail, rows, raw_fold, stream);
+        ZpParams Pk = P;
+        Pk.raw_edge_loop = raw_edge_loop ? 1 : 0;
+        launch_pz_raw<Q, S, EDGE, FMT8>(Pk, iq, stride, b_tail, rows, raw_fold, stream);
     }
     template <class Src>
     void lp2(const Lp2Params &P, const Src &src, int rows)
@@ -1011,6 +1015,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
     be.timer = &plan->timer;
     be.device = plan->device;
     be.raw_fold = plan->raw_fold;
+    be.raw_edge_loop = debug_value("raw_edge_fill") == 0;
     if (plan->mode == TDM_MODE_TETRA || plan->mode == TDM_MODE_TETRA_GARDNER) {
         if (pre_shift_hz || freq_offset_hz)
             return fail(TDM_ERR_UNSUPPORTED, "TETRA mode: carrier offsets are estimated, not supplied");

@@ -86,6 +86,10 @@ struct ZpParams {
     double *Hb;     // [rows][nb][D] c128, resolved backward carry into each block
     // ---- parallel-form stage (pz_kernels.hpp / pz_tables.hpp); pform == 0 for the cascade engine
     int32_t pform;
+    // raw-integer kernel, wide blocks: 0 = the edge lanes' samples are built by the whole wavefront (the shipped path; what
+    // every zeroed ZpParams gets), 1 = by each edge lane itself in a rolled loop (tdm_debug_set "raw_edge_fill" 0, the A/B
+    // partner).  Sits in the padding behind pform: no kernel's argument layout moves.
+    int32_t raw_edge_loop;
     const double *pz;   // constant block, layout PzLayout
     double *Elast;      // [rows][D] c128, causal lane state exported by the last block (see pz_tables.hpp)
 };
