@@ -120,6 +120,11 @@ TDM_API int tdm_last_error(char *buf, size_t buflen);
  *   "raw_edge_fill"   0: the raw-byte decimator's first and tail blocks have each lane that holds extension or pad samples
  *                     fetch them itself, one at a time, instead of the whole wavefront building them together.  Read at
  *                     every tdm_process* call, not when the plan is made; equal results bit for bit           (default 1)
+ *   "scan_prune"      0: the raw-byte decimator of plans created from now on runs the scans of its lanes' end states with
+ *                     every term, instead of without the terms whose weight |pole|^(lane distance) is under 1e-24 of the
+ *                     states they would be added to (a compile-time table per factor, checked against the plan's own
+ *                     filter design when the plan is made; a design it does not fit runs every term whatever the
+ *                     switch says).  Equal results bit for bit                                              (default 1)
  *   "gardner_fused"   0: TDM_MODE_TETRA_GARDNER as three launches (matched filter -> HBM -> loop -> decisions)  (default 1)
  *   "gardner_segments" what tdm_plan_option "gardner_segments" sets per plan, for TDM_MODE_TETRA_GARDNER plans created from
  *                     now on: 0 whole chunks, 1 the default, K > 1 at most K pieces, -1 fitted to the batch   (default 1)

@@ -67,6 +67,26 @@ struct WaveComm {
             ob[k] = ok ? y : 0.0;
         }
     }
+    // step 1 of the two above for the neighbouring row only (pz_row_total_near2): row 2 <- lane 31 (the same row_bcast:31
+    // under a row mask of row 2 alone: the masked-out rows keep the 0 they are given); row 1 <- lane 32; 0 elsewhere
+    static constexpr bool kRowTotalNear = true;
+    template <int K>
+    __device__ __forceinline__ void row_total_prev2_near(const double *a, const double *b, double *oa, double *ob)
+    {
+        dpp2<K, 0x143, 0x4, false>(a, b, oa, ob);
+    }
+    template <int K>
+    __device__ __forceinline__ void row_total_next2_near(const double *a, const double *b, double *oa, double *ob)
+    {
+        const int lane = threadIdx.x & 63;
+        const bool ok = (lane & 48) == 16;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double x = __shfl(a[k], 32, 64), y = __shfl(b[k], 32, 64);
+            oa[k] = ok ? x : 0.0;
+            ob[k] = ok ? y : 0.0;
+        }
+    }
     // whole-wave shift by one lane, 0 shifted in
     template <int K>
     __device__ __forceinline__ void wave_shr1(const double *a, const double *b, double *oa, double *ob) { dpp2<K, 0x138, 0xf, true>(a, b, oa, ob); }

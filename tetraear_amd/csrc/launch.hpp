@@ -14,9 +14,10 @@ void launch_zp_block(const ZpParams &P, const Loader &ld, int nb, int rows, hipS
 // parallel-form decimator, samples held as doubles (pz_kernels.hpp)
 template <int Q, int S, int EDGE, bool SHIFT>
 void launch_pz_block(const ZpParams &P, const RawLoaderRT<SHIFT> &ld, int nb, int rows, hipStream_t st);
-// parallel-form decimator on the raw bytes; fold = false: narrow blocks sample by sample where a folded form exists
+// parallel-form decimator on the raw bytes; fold = false: narrow blocks sample by sample where a folded form exists;
+// prune = false: the lane scans with every term (pz_tables.hpp PzScanKeep)
 template <int Q, int S, int EDGE, int FMT8>
-void launch_pz_raw(const ZpParams &P, const void *iq, int64_t stride, int b_tail, int rows, bool fold, hipStream_t st);
+void launch_pz_raw(const ZpParams &P, const void *iq, int64_t stride, int b_tail, int rows, bool fold, bool prune, hipStream_t st);
 // low-rate stage in one kernel (lp2_kernels.hpp)
 template <class Src>
 void launch_lp2(const Lp2Params &P, const Src &src, int rows, hipStream_t st);

@@ -16,6 +16,8 @@
 // Geometry: a lane owns L = S*Q consecutive samples, Q = decimation factor, so every lane's outputs sit at
 // its local positions 0, Q, 2Q, ... (compile-time); a wavefront owns a block of 64 lanes.
 #pragma once
+#include <type_traits>
+
 #include "zp_kernels.hpp"
 #include "pz_tables.hpp"
 
@@ -270,10 +272,43 @@ struct RawLoaderRT {
 //   Comm: edge_slots() -> PzEdgeGeom<L,EDGE>::kDoubles doubles of wavefront-private scratch (pz_raw_body: PzRawScratch);
 //   shfl_up2<2> / shfl_down2<2> as in zp_block_body.
 // ------------------------------------------------------------------------------------------
+// The second row-total step of a pair whose multiply by C^(16 L) is left out: only the row next to the source lane takes
+// the total (row 2 <- lane 31, row 1 <- lane 32), the row beyond it takes 0 like the rows that never had a source.  A Comm
+// that says kRowTotalNear does that in the shuffle itself; any other gets the ordinary shuffle and a select.
+template <class Comm, class = void>
+struct PzCommRowTotalNear { static constexpr bool value = false; };
+template <class Comm>
+struct PzCommRowTotalNear<Comm, std::void_t<decltype(Comm::kRowTotalNear)>> { static constexpr bool value = Comm::kRowTotalNear; };
+
+template <class Comm>
+TDM_HD void pz_row_total_near2(Comm &cm, int lane, const double *zr, const double *zq, double *jr, double *jq, const double *ur,
+                               const double *uq, double *kr, double *kq)
+{
+    if constexpr (PzCommRowTotalNear<Comm>::value) {
+        cm.template row_total_prev2_near<2>(zr, zq, jr, jq);
+        cm.template row_total_next2_near<2>(ur, uq, kr, kq);
+    } else {
+        cm.template row_total_prev2<2>(zr, zq, jr, jq, 1);
+        cm.template row_total_next2<2>(ur, uq, kr, kq, 1);
+        const bool far_f = lane >= 48, far_b = lane < 16;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            jr[k] = far_f ? 0.0 : jr[k]; jq[k] = far_f ? 0.0 : jq[k];
+            kr[k] = far_b ? 0.0 : kr[k]; kq[k] = far_b ? 0.0 : kq[k];
+        }
+    }
+}
+
 // Phases 2 and 3 of a block, shared by the kernels that differ in how a lane holds its samples: scans of the lane
 // end states, exports of the block's end states, start-state responses at the lane's outputs, block-local outputs
 // (minus `y_const`: the response to a constant input offset that a kernel working on raw integers leaves out).
-template <int Q, int S, int EDGE, class Comm>
+// Keep::kept(s): the scan terms pair s keeps (pz_tables.hpp PzScanKeep; PzScanKeepAll: every term).  A term that is left
+// out is not there at all -- no shuffle, no table load, no multiply-add --; a kept one has the operands and the place it
+// has with every term kept.
+// BLOCK_STORE_TEST: the S outputs of a lane are stored under ONE wave-uniform test where the whole block lies inside the
+// row (every block but a row's first and last ones) instead of under S per-output tests; the values stored are the same.
+// The raw-integer kernel asks for it; the double-based one keeps the per-output tests it always had.
+template <int Q, int S, int EDGE, class Keep = PzScanKeepAll, bool BLOCK_STORE_TEST = false, class Comm>
 TDM_HD void pz_block_finish(const ZpParams &P, Comm &cm, int lane, int blk, int row, double (*zr)[2], double (*zq)[2],
                             double (*ur)[2], double (*uq)[2], double *yr, double *yi, double y_const)
 {
@@ -308,6 +343,7 @@ TDM_HD void pz_block_finish(const ZpParams &P, Comm &cm, int lane, int blk, int 
         double jr[NP][2], jq[NP][2], kr[NP][2], kq[NP][2];
 #pragma unroll
         for (int s = 0; s < NP; ++s) {
+            if (Keep::kept(s) <= j) continue;
             cm.template row_shr2<2>(zr[s], zq[s], jr[s], jq[s], d);   // lane - d of the same row, 0 where there is none
             cm.template row_shl2<2>(ur[s], uq[s], kr[s], kq[s], d);   // lane + d
         }
@@ -315,6 +351,7 @@ TDM_HD void pz_block_finish(const ZpParams &P, Comm &cm, int lane, int blk, int 
         TDM_OPAQUE_SPTR(Mj);
 #pragma unroll
         for (int s = 0; s < NP; ++s) {
+            if (Keep::kept(s) <= j) continue;
             const auto M = TDM_CPTR(Mj + (size_t)s * kScanSteps * 4);
             const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3];
             zr[s][0] = fma(m0, jr[s][0], fma(m1, jr[s][1], zr[s][0]));
@@ -333,6 +370,10 @@ TDM_HD void pz_block_finish(const ZpParams &P, Comm &cm, int lane, int blk, int 
         double jr[NP][2], jq[NP][2], kr[NP][2], kq[NP][2];
 #pragma unroll
         for (int s = 0; s < NP; ++s) {
+            if (step == 1 && Keep::kept(s) <= 4) {
+                pz_row_total_near2(cm, lane, zr[s], zq[s], jr[s], jq[s], ur[s], uq[s], kr[s], kq[s]);
+                continue;
+            }
             cm.template row_total_prev2<2>(zr[s], zq[s], jr[s], jq[s], step);   // step 0: rows 1,3 <- lane 15 of rows 0,2; step 1: rows 2,3 <- lane 31
             cm.template row_total_next2<2>(ur[s], uq[s], kr[s], kq[s], step);   // mirror image: rows 0,2 <- lane 0 of rows 1,3; rows 0,1 <- lane 32
         }
@@ -342,6 +383,7 @@ TDM_HD void pz_block_finish(const ZpParams &P, Comm &cm, int lane, int blk, int 
             TDM_OPAQUE_SPTR(M16);
 #pragma unroll
             for (int s = 0; s < NP; ++s) {
+                if (Keep::kept(s) <= 4) continue;
                 const auto M = TDM_CPTR(M16 + (size_t)s * kScanSteps * 4);
                 const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3];
                 const bool far_f = lane >= 48, far_b = lane < 16;
@@ -416,7 +458,13 @@ TDM_HD void pz_block_finish(const ZpParams &P, Comm &cm, int lane, int blk, int 
         static_assert((G::P0 + EDGE) % Q == 0 || S == 0, "outputs sit on lane-local multiples of Q");
         const int64_t j0 = ((int64_t)blk * Bn + (int64_t)lane * L - P.k0L) / Q;   // exact: every term is a multiple of Q
         f64x2 *y0 = (f64x2 *)(P.y0 + (int64_t)row * P.n_out * 2);
-        if ((int64_t)blk * Bn + (int64_t)lane * L >= P.k0L) {
+        // (one test for the wavefront: only block 0 has lanes before the row's first output, only a row's last block(s) a
+        //  lane whose outputs cross n_out)
+        const bool all_inside = BLOCK_STORE_TEST && (int64_t)blk * Bn >= P.k0L && ((int64_t)(blk + 1) * Bn - P.k0L) / Q <= P.n_out;
+        if (all_inside) {
+#pragma unroll
+            for (int t = 0; t < S; ++t) y0[j0 + t] = f64x2{yr[t] - y_const, yi[t] - y_const};
+        } else if ((int64_t)blk * Bn + (int64_t)lane * L >= P.k0L) {
 #pragma unroll
             for (int t = 0; t < S; ++t)
                 if (j0 + t < P.n_out) y0[j0 + t] = f64x2{yr[t] - y_const, yi[t] - y_const};
@@ -905,7 +953,9 @@ TDM_HD void pz_raw_fill_edges(Comm &cm, const char *rowp, int64_t n, int blk, in
     }
 }
 
-template <int Q, int S, int EDGE, int FMT8, bool WIDE, bool FOLD = true, class Comm>
+// PRUNE: the scans without the terms PzScanKeep<Q, S> leaves out (what ships); false: every term (tdm_debug_set
+// "scan_prune" 0, and any plan whose design the compiled table does not fit)
+template <int Q, int S, int EDGE, int FMT8, bool WIDE, bool FOLD = true, bool PRUNE = true, class Comm>
 TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, Comm &cm, int lane, int blk, int row)
 {
     constexpr int NP = PzLayout::kMaxPairs;
@@ -1071,7 +1121,8 @@ TDM_HD void pz_raw_body(const ZpParams &P, const void *iq, int64_t row_stride, C
             ur[s][0] = a1r[s]; ur[s][1] = a2r[s]; uq[s][0] = a1q[s]; uq[s][1] = a2q[s];
         }
     }
-    pz_block_finish<Q, S, EDGE>(P, cm, lane, blk, row, zr, zq, ur, uq, yr, yi, pz[PzLayout::off_yc]);
+    typedef std::conditional_t<PRUNE, PzScanKeep<Q, S>, PzScanKeepAll> Keep;
+    pz_block_finish<Q, S, EDGE, Keep, true>(P, cm, lane, blk, row, zr, zq, ur, uq, yr, yi, pz[PzLayout::off_yc]);
     // the last extended sample, as an integer: 2 u[n-1] - u[n-1-edge]
     if (blk == P.nb - 1 && lane == 0) {
         int ar, ai, br, bi;

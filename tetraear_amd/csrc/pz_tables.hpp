@@ -61,6 +61,40 @@ struct PzLayout {
     TDM_HD static int size(int S) { return off_fold_dx(S) + 2; }
 };
 
+// ---- scan terms of the raw-integer kernel that are numerically nothing (pz_block_finish, phase 2).  A lane's inclusive
+// state takes the state d lanes away through C^(L d): the four Kogge-Stone steps inside a row of 16 lanes (terms 0..3, d =
+// 1, 2, 4, 8) and the multiply by C^(16 L) that carries a row total over a whole row in the second row-total step (term 4,
+// d = 16).  |C^(L d)| decays like |p|^(L d), p the pair's pole; a term whose bound |p|^(L d) lies under kPzScanNegligible
+// is left out of the kernel.  The constant is the one lp2_tables.hpp holds the low-rate kernel's scan_rows to.  The
+// row-total steps themselves always stay: their distance depends on the lane (1 .. 16).
+// The bounds fall with d, so a pair's kept terms are the first kept(s) of the five.  The kernel's choice is compile-time:
+// one table per (Q, S) of the raw-integer kernel below, pairs in the design's own order (design_cheby1_8: the pair
+// closest to the unit circle LAST).  The tables hold what the rule gives for cheby1(8, 0.05, 0.8 / Q); a plan checks its
+// table against its own design (pz_scan_keep_is_safe) and takes the kernel with every term if one compiled-out term is not
+// under the constant.
+constexpr long double kPzScanNegligible = 1e-24L;
+constexpr int kPzScanTerms = 5;
+struct PzScanKeepAll {
+    TDM_HD static constexpr int kept(int) { return kPzScanTerms; }
+};
+template <int Q, int S>
+struct PzScanKeep : PzScanKeepAll {};
+#define TDM_PZ_SCAN_KEEP(Q, S, K0, K1, K2, K3)                                                                \
+    template <>                                                                                               \
+    struct PzScanKeep<Q, S> {                                                                                 \
+        TDM_HD static constexpr int kept(int s) { return s == 0 ? K0 : (s == 1 ? K1 : (s == 2 ? K2 : K3)); } \
+    };
+TDM_PZ_SCAN_KEEP(3, 16, 2, 3, 3, 5)
+TDM_PZ_SCAN_KEEP(4, 16, 2, 3, 3, 5)
+TDM_PZ_SCAN_KEEP(6, 16, 2, 3, 3, 5)
+TDM_PZ_SCAN_KEEP(7, 16, 2, 3, 3, 5)
+TDM_PZ_SCAN_KEEP(8, 15, 2, 3, 3, 5)
+TDM_PZ_SCAN_KEEP(10, 12, 3, 3, 4, 5)
+TDM_PZ_SCAN_KEEP(12, 10, 3, 3, 4, 5)
+TDM_PZ_SCAN_KEEP(13, 8, 3, 4, 4, 5)
+// (41, 2): lanes of 82 samples at poles this close to the circle -- every term stays
+#undef TDM_PZ_SCAN_KEEP
+
 namespace detail {
 typedef long double ldbl;
 typedef std::complex<long double> lcx;
@@ -171,6 +205,22 @@ inline PzDesign design_pz(const double (*sos)[6], int nsec)
         }
     }
     return d;
+}
+
+// the bound |p_s|^(L d) of scan term `term` (d = 2^term lanes of L samples) for pair s of the design: |p_s|^2 = a2[s]
+inline detail::ldbl pz_scan_bound(const PzDesign &d, int s, int L, int term)
+{
+    return std::pow(d.a2[s], (detail::ldbl)L * (detail::ldbl)(1 << term) / 2);
+}
+
+// kept[s] = scan terms pair s keeps (PzScanKeep<Q, S>::kept, pairs in the design's order): true when every term the table
+// leaves out has its bound under kPzScanNegligible for THIS design
+inline bool pz_scan_keep_is_safe(const PzDesign &d, int L, const int *kept)
+{
+    for (int s = 0; s < d.NP; ++s)
+        for (int term = kept[s] < 0 ? 0 : kept[s]; term < kPzScanTerms; ++term)
+            if (!(pz_scan_bound(d, s, L, term) < kPzScanNegligible)) return false;
+    return true;
 }
 
 // ---- tables.  L = samples per lane (a multiple of out_stride whenever S > 0 outputs per lane are tabulated), S =

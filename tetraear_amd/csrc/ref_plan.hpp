@@ -50,6 +50,17 @@ inline int pz_raw_outputs_per_lane(int q)
     }
 }
 
+// scan terms pair s keeps in the raw-integer kernel of factor q as compiled (pz_tables.hpp PzScanKeep)
+inline int pz_raw_scan_kept(int q, int s)
+{
+    switch (q) {
+#define TDM_PZR_K(Q, S) case Q: return PzScanKeep<Q, S>::kept(s);
+        TDM_PZR_CASES(TDM_PZR_K)
+#undef TDM_PZR_K
+    default: return kPzScanTerms;
+    }
+}
+
 struct RefPlanHost {
     double sample_rate = 0;
     int64_t n = 0;
@@ -75,6 +86,10 @@ struct RefPlanHost {
     int64_t raw_min_blocks = 0;
     ZpHostTables dec_raw;
     Lp2Host lp2_raw;
+    // the compiled table of kept scan terms (PzScanKeep) leaves out nothing that counts for THIS design: pair by pair, in
+    // the tables' own pair order, every compiled-out term's bound is under kPzScanNegligible.  false: the kernel with
+    // every term runs
+    bool raw_scan_prune_ok = false;
 };
 
 // sos rows b = g*[1,2,1], a -> device form (unit numerators, one input gain, matching zi)
@@ -154,6 +169,9 @@ inline RefPlanHost build_ref_plan(double sample_rate, int64_t n, double bandwidt
         h.dec_raw = build_pz_tables(sh, n, h.n_dec);
         h.lp2_raw = build_lp2(h.tf.sos, h.n_dec, kEdgeTf, h.sps, &h.dec_raw, h.sos.sos);
         if (h.lp2_raw.ok) h.raw_S = S;
+        int kept[PzLayout::kMaxPairs];
+        for (int s = 0; s < PzLayout::kMaxPairs; ++s) kept[s] = pz_raw_scan_kept(h.q, s);
+        h.raw_scan_prune_ok = pz_scan_keep_is_safe(sh->dz, h.q * S, kept);
     }
     return h;
 }

@@ -55,6 +55,7 @@ static DebugSwitch g_debug[] = {
     {"raw_min_blocks", {-1}, -1},        // >= 0: blocks below which a batch stays on the double-based decimator (plans made from now on)
     {"raw_fold", {1}, 1},                // 0: plans made from now on run the raw-integer decimator's narrow blocks sample by sample (q = 10)
     {"raw_edge_fill", {1}, 1},           // 0: the raw-integer decimator's wide blocks fill their edge lanes lane by lane (read at every call)
+    {"scan_prune", {1}, 1},              // 0: plans made from now on run the raw-integer decimator's lane scans with every term (PzScanKeep)
     {"gardner_fused", {1}, 1},           // 0: Gardner mode as three launches (matched filter -> HBM -> loop -> decisions)
     {"pfb_direct", {0}, 0},              // 1: channeliser plans made from now on use the direct-DFT kernel
     {"pfb_rounds", {0}, 0},              // > 0: rounds per channeliser workgroup (plans made from now on)
@@ -272,6 +273,7 @@ struct HipBackend {
     int device = 0;
     bool raw_fold = true;   // tdm_debug_set "raw_fold" as the plan saw it
     bool raw_edge_loop = false;   // tdm_debug_set "raw_edge_fill" 0 as this call saw it (ZpParams::raw_edge_loop)
+    bool scan_prune = true;   // tdm_debug_set "scan_prune" as the plan saw it, and the plan's design fits the compiled table
 
     struct Scope {
         HipBackend &be; int stage; Event a, b; bool on;
@@ -305,7 +307,7 @@ struct HipBackend {
         Scope s(*this, ST_DEC_BLOCK);
         ZpParams Pk = P;
         Pk.raw_edge_loop = raw_edge_loop ? 1 : 0;
-        launch_pz_raw<Q, S, EDGE, FMT8>(Pk, iq, stride, b_tail, rows, raw_fold, stream);
+        launch_pz_raw<Q, S, EDGE, FMT8>(Pk, iq, stride, b_tail, rows, raw_fold, scan_prune, stream);
     }
     template <class Src>
     void lp2(const Lp2Params &P, const Src &src, int rows)
@@ -434,6 +436,7 @@ struct tdm_plan {
     int32_t rows_per_chunk = 1;   // tdm_plan_option "rows_per_chunk"
     int64_t raw_min_blocks = 0;
     bool raw_fold = true;         // tdm_debug_set "raw_fold" when the plan was made
+    bool scan_prune = true;       // tdm_debug_set "scan_prune" when the plan was made
     std::map<int64_t, std::unique_ptr<Variant>> variants;
     Variant *cur = nullptr;
     uint64_t clock = 0;
@@ -890,6 +893,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
     // (tdm_debug_set("no_raw", 1): experiments / tests keep cu8 plans on the kernel that holds its samples as doubles)
     p->allow_raw = debug_value("no_raw") != 1;
     p->raw_fold = debug_value("raw_fold") != 0;
+    p->scan_prune = debug_value("scan_prune") != 0;
     {
         // blocks of the double-based decimator below which a batch stays on it: two wavefronts per SIMD of the device
         // (tdm_debug_set("raw_min_blocks", n) overrides; tests use 0 to put single carriers on the raw-integer kernel)
@@ -1015,6 +1019,8 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
     be.timer = &plan->timer;
     be.device = plan->device;
     be.raw_fold = plan->raw_fold;
+    // (RefPlanHost::raw_scan_prune_ok: the check of the compiled table against this plan's design, build_ref_plan)
+    be.scan_prune = plan->scan_prune && plan->cur && plan->cur->h.raw_scan_prune_ok;
     be.raw_edge_loop = debug_value("raw_edge_fill") == 0;
     if (plan->mode == TDM_MODE_TETRA || plan->mode == TDM_MODE_TETRA_GARDNER) {
         if (pre_shift_hz || freq_offset_hz)
