@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TDM_VERSION 103 /* 0.1.3: + tdm_stream_* and tdm_link_ceiling (0.1.2: + tdm_plan_wait_for; 0.1.1: tdm_plan_info grew by gardner_segments) -- a binding checks tdm_version() against the header it was written for */
+#define TDM_VERSION 103 /* 0.1.3: + tdm_stream_* and tdm_link_ceiling; TDM_CS16 joined tdm_fmt without a new export or a changed layout, so the number stayed (0.1.2: + tdm_plan_wait_for; 0.1.1: tdm_plan_info grew by gardner_segments) -- a binding checks tdm_version() against the header it was written for */
 
 #if defined(__GNUC__)
 #define TDM_API __attribute__((visibility("default")))
@@ -47,12 +47,19 @@ typedef enum tdm_status {
 } tdm_status;
 
 /* IQ sample formats accepted on the wire (signal/capture.py:143-158 hands over complex128
- * made by pyrtlsdr from cu8; cu8 is the RTL-SDR native format). */
+ * made by pyrtlsdr from cu8; cu8 is the RTL-SDR native format; cs16 is what the 10 MS/s radios' drivers hand over --
+ * USRP, bladeRF, LimeSDR, Airspy, SDRplay: "sc16" / "CS16").  Rows and streams of a format are aligned to one component
+ * of it and no more (cs16: 2-byte components, so a sample is 4-byte aligned when the row starts on one); any row stride
+ * in samples is legal. */
 typedef enum tdm_fmt {
     TDM_CU8 = 0,  /* uint8 I,Q;  value = u/127.5 - 1   (pyrtlsdr convention) */
     TDM_CS8 = 1,  /* int8  I,Q;  value = s/128.0 */
     TDM_CF32 = 2, /* float I,Q */
-    TDM_CF64 = 3  /* double I,Q  (numpy complex128, the reference's own dtype) */
+    TDM_CF64 = 3, /* double I,Q  (numpy complex128, the reference's own dtype) */
+    TDM_CS16 = 4  /* int16 I,Q, little-endian, 4 bytes a sample;  value = s/32768.0 exactly (-32768 is -1.0, nothing is
+                     clipped).  Converted where a kernel loads it: exact in fp32 and fp64, so every entry point computes what
+                     it computes for the same values handed over as cf32 (channeliser, TETRA modes) or cf64 (reference mode,
+                     spectrum gate), bit for bit */
 } tdm_fmt;
 /* Input range.  Reference mode equals the reference for components of magnitude up to 2^1005 (from about 2^1006 the
  * device's parallel-form filters overflow where the reference's cascade still has room; the reference itself fails from
@@ -94,7 +101,7 @@ typedef struct tdm_plan_info {
     int32_t device;
     int32_t dec_engine;   /* decimator kernel the next call runs: 0 none, 1 cascade engine, 2 parallel form on doubles,
                              3 parallel form on the raw bytes (cu8 batches of at least 8 blocks per CU; never a plan with
-                             rows_per_chunk > 1) */
+                             rows_per_chunk > 1; never cs16, which runs engine 1 or 2 as cs8 and cf32 do) */
     int32_t gardner_segments; /* TDM_MODE_TETRA_GARDNER: the number of independently started loops every carrier's chunk is
                              walked as, joined at seams: by default the largest of 2, 4, 8 that leaves every loop its 384
                              warm-up symbols -- a function of the chunk (length, rate, taps) alone, never of the batch --
@@ -138,10 +145,11 @@ TDM_API int tdm_debug_get(const char *key, int64_t *value);
 /* ---- plan: one (sample_rate, n_samples, n_carriers, format) configuration ----------------
  * replaces SignalProcessor.__init__ (processor.py:21-33) + the per-call filter design
  * (processor.py:78, :254).  n_carriers independent streams are processed per call.
- * in_fmt: reference mode takes all four wire formats; the TETRA modes take TDM_CF32 (the channeliser's output) or
- * TDM_CU8 / TDM_CS8 straight off the wire (converted where the kernels stage their window: cu8 as u / 127.5 - 1, cs8 as s / 128;
- * TDM_MODE_TETRA_GARDNER's fused kernel takes bytes at 33 and 35 taps -- 72 and 80 kS/s --, other rates run as three launches,
- * whole chunks).                                                                            */
+ * in_fmt: reference mode takes all five wire formats; the TETRA modes take TDM_CF32 (the channeliser's output) or
+ * TDM_CU8 / TDM_CS8 / TDM_CS16 straight off the wire (converted where the kernels stage their window: cu8 as u / 127.5 - 1, cs8
+ * as s / 128, cs16 as s / 32768 -- the latter then runs the cf32 arithmetic, bit for bit the cf32 call on the same values;
+ * TDM_MODE_TETRA_GARDNER's fused kernel takes bytes at 33 and 35 taps -- 72 and 80 kS/s --, other rates, and cs16 at every rate,
+ * run as three launches, whole chunks).                                                     */
 TDM_API int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, int32_t in_fmt,
                     int32_t mode, int32_t device, tdm_plan **out);
 TDM_API int tdm_plan_destroy(tdm_plan *plan);
@@ -305,7 +313,8 @@ typedef struct tdm_stream_result {
     const int32_t *best_phase;
     const double *min_margin;
 } tdm_stream_result;
-/* sample_rate, n_samples (the chunk: samples per input row), n_rows (plan rows), in_fmt, mode: as tdm_plan_create;
+/* sample_rate, n_samples (the chunk: samples per input row), n_rows (plan rows), in_fmt, mode: as tdm_plan_create, except that
+ * in_fmt is one of TDM_CU8 .. TDM_CF64 (TDM_CS16 is TDM_ERR_INVALID here: a host-fed cs16 stream is not built);
  * depth >= 1 (slots = plans); freq_offset_hz / pre_shift_hz [n_rows] or NULL (pre_shift_hz: TDM_MODE_REFERENCE only);
  * rows_per_chunk: 1, or C dividing n_rows (TDM_MODE_REFERENCE).  Arguments are checked before any HIP call. */
 TDM_API int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int32_t in_fmt, int32_t mode,
@@ -375,7 +384,7 @@ TDM_API int tdm_find_sync(const uint8_t *units, int64_t row_stride, const int32_
                           int32_t *n_pos, double *max_corr, int32_t device_pointers, int32_t device);
 
 /* ---- tetra-mode channeliser: oversampled polyphase DFT filter bank (no counterpart in the reference) --
- * One wideband stream (cu8 / cs8 / cf32, n_in samples at fs) -> M channels spaced fs/M, each decimated by
+ * One wideband stream (cu8 / cs8 / cs16 / cf32, n_in samples at fs) -> M channels spaced fs/M, each decimated by
  * D (output rate fs/D), out [M][n_out] cf32 with n_out = ceil(n_in/D); channel k is centred on k*fs/M
  * (k >= M/2: negative frequencies).  Built for M in {72, 80, 96, 128, 400}.                          */
 TDM_API int tdm_channelise(const void *iq, int32_t in_fmt, int64_t n_in, int32_t M, int32_t D, float *out,
@@ -395,7 +404,7 @@ TDM_API int tdm_channelise_batch(const void *iq, int32_t in_fmt, int64_t n_in, i
  * object keeps, per stream, the last L-1 = 3M-1 input samples (in wire format) and the stream's position, so that the
  * outputs of consecutive pushes, concatenated along time, equal ONE tdm_channelise_batch over the concatenated input, bit
  * for bit (output m of a stream sits at its absolute input instant m*D; oracle/pfb_np.py over the whole stream).
- *   create    M, in_fmt (cu8 / cs8 / cf32), kernel choice as tdm_channelise_batch; every stream of the object advances
+ *   create    M, in_fmt (cu8 / cs8 / cs16 / cf32), kernel choice as tdm_channelise_batch; every stream of the object advances
  *             by the same n_in per push, n_in <= max_n_in.  Checks its arguments before any HIP call and allocates
  *             everything (history, host-form staging sized by max_n_in); a push allocates nothing.
  *   push      iq [n_streams][n_in] back to back, out [n_streams][M][out_pitch] cf32 with out_pitch >= ceil(n_in/D), the

@@ -10,9 +10,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TETRAHIP_LIB", os.path.join(_HERE, "libtetrahip.so"))  # override: experiments only
 
-FMT_CU8, FMT_CS8, FMT_CF32, FMT_CF64 = 0, 1, 2, 3
+FMT_CU8, FMT_CS8, FMT_CF32, FMT_CF64, FMT_CS16 = 0, 1, 2, 3, 4
 MODE_REFERENCE, MODE_TETRA, MODE_TETRA_GARDNER = 0, 1, 2
-FMT_BYTES = {FMT_CU8: 2, FMT_CS8: 2, FMT_CF32: 8, FMT_CF64: 16}
+FMT_BYTES = {FMT_CU8: 2, FMT_CS8: 2, FMT_CF32: 8, FMT_CF64: 16, FMT_CS16: 4}
 
 
 class TetraHipError(RuntimeError):

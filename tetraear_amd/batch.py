@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FMT_BYTES, FMT_CF32, FMT_CF64, FMT_CS8, FMT_CU8, MODE_REFERENCE, PlanInfo, check, ptr
+from ._lib import FMT_BYTES, FMT_CF32, FMT_CF64, FMT_CS8, FMT_CS16, FMT_CU8, MODE_REFERENCE, PlanInfo, check, ptr
 
-_FMT_OF = {"cu8": FMT_CU8, "cs8": FMT_CS8, "cf32": FMT_CF32, "cf64": FMT_CF64}
+_FMT_OF = {"cu8": FMT_CU8, "cs8": FMT_CS8, "cf32": FMT_CF32, "cf64": FMT_CF64, "cs16": FMT_CS16}
 
 
 class DeviceBuffer:
@@ -213,9 +213,9 @@ class BatchDemodulator:
 
     def rrc_filter(self, iq):
         """host in, host out: [n_carriers][n_samples] in the plan's wire format (complex64; for cu8 / cs8 plans interleaved
-        bytes) -> the matched filter's output as complex64, same shape"""
-        if self.fmt in (FMT_CU8, FMT_CS8):
-            iq = np.ascontiguousarray(iq).view(np.uint8).reshape(self.n_carriers, 2 * self.n_samples)
+        bytes, for cs16 plans interleaved int16) -> the matched filter's output as complex64, same shape"""
+        if self.fmt in (FMT_CU8, FMT_CS8, FMT_CS16):
+            iq = np.ascontiguousarray(iq).view(np.uint8).reshape(self.n_carriers, FMT_BYTES[self.fmt] * self.n_samples)
         else:
             iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(self.n_carriers, self.n_samples)
         pitch = (self.n_samples + 1) & ~1

@@ -11,7 +11,7 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import FMT_BYTES, check, ptr
 
-_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2}
+_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cs16": 4}
 
 
 def channelise(iq, fmt, M, D, device=0):

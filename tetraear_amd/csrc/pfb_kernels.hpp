@@ -24,7 +24,7 @@ constexpr int kPfbThreads = 256;
 struct PfbParams {
     int32_t D;        // decimation
     int32_t T;        // output times per workgroup
-    int32_t fmt;      // TDM_CU8 / TDM_CS8 / TDM_CF32
+    int32_t fmt;      // TDM_CU8 / TDM_CS8 / TDM_CF32 / TDM_CS16
     int32_t pad_;
     int64_t n_in, n_out;
     const float *h;       // [M*P] prototype
@@ -47,12 +47,13 @@ struct PfbParams {
 };
 
 // the input format's bytes per sample
-__host__ __device__ constexpr int pfb_fmt_bytes(int fmt) { return fmt == 2 ? 8 : 2; }
-// one past the last history sample of stream y (local index n < 0 lives at byte n * pfb_fmt_bytes from here), or nullptr
+__host__ __device__ constexpr int pfb_fmt_bytes(int fmt) { return fmt == 2 ? 8 : (fmt == 4 ? 4 : 2); }
+// one past the last history sample of stream y (local index n < 0 lives at byte n * fb from here, fb = the format's bytes per
+// sample), or nullptr
 template <int L>
-__device__ __forceinline__ const char *pfb_hist_end(const PfbParams &Q, int y)
+__device__ __forceinline__ const char *pfb_hist_end(const PfbParams &Q, int y, int fb)
 {
-    return Q.hist ? (const char *)Q.hist + (int64_t)y * Q.hist_stride + (int64_t)(L - 1) * pfb_fmt_bytes(Q.fmt) : nullptr;
+    return Q.hist ? (const char *)Q.hist + (int64_t)y * Q.hist_stride + (int64_t)(L - 1) * fb : nullptr;
 }
 
 
@@ -64,6 +65,9 @@ __device__ __forceinline__ float2 pfb_load(const void *iq, int fmt, int64_t n)
     } else if (fmt == 1) {
         const int8_t *p = (const int8_t *)iq + 2 * n;
         return make_float2((float)p[0] * (1.f / 128.f), (float)p[1] * (1.f / 128.f));
+    } else if (fmt == 4) {  // cs16: s / 32768, exact
+        const int16_t *p = (const int16_t *)iq + 2 * n;
+        return make_float2((float)p[0] * 0x1p-15f, (float)p[1] * 0x1p-15f);
     }
     return ((const float2 *)iq)[n];
 }
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(kPfbThreads) void k_pfb(const void *__restrict__ iq
     const int64_t m0 = (int64_t)blockIdx.x * T;
     iq = (const char *)iq + (int64_t)blockIdx.y * Q.in_stride;
     out += (int64_t)blockIdx.y * Q.out_batch;
-    const char *hend = pfb_hist_end<L>(Q, blockIdx.y);
+    const char *hend = pfb_hist_end<L>(Q, blockIdx.y, pfb_fmt_bytes(Q.fmt));
     // ---- stage 0: inputs n = o + m0*D - (L-1) + i; n < 0 from the history (one load expression for both sources)
     const int64_t nbase = Q.o + m0 * D - (L - 1);
     for (int i = tid; i < nxs; i += kPfbThreads) {
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(kPfbThreads) void k_pfb(const void *__restrict__ iq
 // ---- register-FFT variant ---------------------------------------------------------------------
 // Workgroup = TB*M2 threads, TB consecutive output times per round, G rounds, any decimation D.
 //   load     the round's input window arrives as 4-sample units prefetched into registers during
-//            the previous round (one 8-byte load per unit for cu8/cs8, two 16-byte loads for cf32),
+//            the previous round (one 8-byte load per unit for cu8/cs8, one 16-byte load for cs16, two for cf32),
 //            converted and written to LDS with 16-byte stores
 //   stage A  item = (branch r, group of 4 output times): the P taps of the branch stay in registers,
 //            lanes walk consecutive r (conflict-free LDS reads and writes); the circular shift
@@ -204,6 +208,45 @@ struct PfbUnit<2> {
     {
         ((float4 *)dst)[0] = a;
         ((float4 *)dst)[1] = b;
+    }
+};
+template <>
+struct PfbUnit<4> {   // cs16: 16 bytes at a 4-byte aligned address; a word is int16 I (low half), int16 Q
+    uint4 v;
+    uint32_t ok;
+    __device__ __forceinline__ void load(const char *base, const char *hend, int64_t hv, int64_t n0, int64_t n_in)
+    {
+        v = make_uint4(0u, 0u, 0u, 0u);
+        if (n0 >= 0 && n0 + 3 < n_in) {
+            __builtin_memcpy(&v, base + n0 * 4, 16);
+            ok = 15u;
+        } else {
+            ok = 0;
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t n = n0 + c;   // the push (n >= 0) or the history (-hv <= n < 0), in wire format either way
+                if (n >= 0 ? n < n_in : n >= -hv) {
+                    w[c] = ((const uint32_t *)(n >= 0 ? base : hend))[n];
+                    ok |= 1u << c;
+                }
+            }
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+    __device__ __forceinline__ static cf32v conv(uint32_t w)
+    {
+        return cv((float)(int16_t)(w & 65535u), (float)((int32_t)w >> 16)) * 0x1p-15f;
+    }
+    __device__ __forceinline__ void store(cf32v *dst) const
+    {
+        // (a sample that is not there was loaded as zero bits, which convert to 0.0: no mask needed)
+        const cf32v s0 = conv(v.x), s1 = conv(v.y), s2 = conv(v.z), s3 = conv(v.w);
+        float4 lo, hi;
+        lo.x = s0.x; lo.y = s0.y; lo.z = s1.x; lo.w = s1.y;
+        hi.x = s2.x; hi.y = s2.y; hi.z = s3.x; hi.w = s3.y;
+        ((float4 *)dst)[0] = lo;
+        ((float4 *)dst)[1] = hi;
     }
 };
 template <int FMT>
@@ -359,7 +402,7 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
     // (in LDS rather than re-read from memory: loads and stores share vmcnt, so a global load issued after
     //  pass 2's stores would wait for their write acknowledgements)
     const char *iq = (const char *)iq_ + (int64_t)blockIdx.y * Q.in_stride;
-    const char *hend = CARRY ? pfb_hist_end<L>(Q, blockIdx.y) : nullptr;
+    const char *hend = CARRY ? pfb_hist_end<L>(Q, blockIdx.y, pfb_fmt_bytes(FMT)) : nullptr;
     const int64_t hv = CARRY ? Q.hist_valid : 0, o = CARRY ? Q.o : 0;
     cf32v *out = out_ + (int64_t)blockIdx.y * Q.out_batch;
     const int tid = threadIdx.x;
@@ -426,7 +469,7 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
 
 // ---- carried state of tdm_channeliser -----------------------------------------------------------------
 // The next history of every stream after a push (chan_stream.hpp chan_hist_source): slot j of new_h = the last L-1 samples
-// of (old_h || this push), copied in wire format (W: uint16_t for cu8 / cs8, uint2 for cf32).  old_h and new_h are two
+// of (old_h || this push), copied in wire format (W: uint16_t for cu8 / cs8, uint32_t for cs16, uint2 for cf32).  old_h and new_h are two
 // different buffers, so a push shorter than L-1 never shifts a buffer onto itself.  grid.y = stream; strides in samples.
 template <typename W>
 __global__ __launch_bounds__(256) void k_pfb_hist(const W *__restrict__ iq, int64_t in_stride, const W *__restrict__ old_h,

@@ -82,7 +82,7 @@ struct RawLoaderRT {
     // C carriers shifted out of each of T consecutive chunks of one stream in one call (plan rows = T x C)
     int32_t rows_per_chunk;
 
-    TDM_HD int bytes() const { return (fmt == FMT_CU8 || fmt == FMT_CS8) ? 2 : (fmt == FMT_CF32 ? 8 : 16); }
+    TDM_HD int bytes() const { return (fmt == FMT_CU8 || fmt == FMT_CS8) ? 2 : (fmt == FMT_CS16 ? 4 : (fmt == FMT_CF32 ? 8 : 16)); }
     TDM_HD const void *row_ptr(int row) const { return (const char *)iq + (int64_t)(rows_per_chunk > 1 ? row / rows_per_chunk : row) * row_stride * bytes(); }
     TDM_HD double row_shift(int row) const { return (SHIFT && pre_shift) ? pre_shift[row] : 0.0; }
 
@@ -92,6 +92,7 @@ struct RawLoaderRT {
         case FMT_CU8: convert_one<FMT_CU8>(rowp, k, re, im); break;
         case FMT_CS8: convert_one<FMT_CS8>(rowp, k, re, im); break;
         case FMT_CF32: convert_one<FMT_CF32>(rowp, k, re, im); break;
+        case FMT_CS16: convert_one<FMT_CS16>(rowp, k, re, im); break;
         default: convert_one<FMT_CF64>(rowp, k, re, im); break;
         }
     }
@@ -203,6 +204,23 @@ struct RawLoaderRT {
                     const f32x2_a4 t = v[i];
                     xr[i] = (double)t.x;
                     xi[i] = (double)t.y;
+                }
+            } break;
+            case FMT_CS16: {   // one word per sample (int16 I low, Q high), rows are 4-byte aligned: 16-byte loads of 4 samples
+                constexpr int NQ = L / 4;
+                const u32x4_a4 *v = (const u32x4_a4 *)p;
+                uint32_t w[L];
+#pragma unroll
+                for (int c = 0; c < NQ; ++c) {
+                    const u32x4_a4 t = v[c];
+                    w[4 * c] = t.x; w[4 * c + 1] = t.y; w[4 * c + 2] = t.z; w[4 * c + 3] = t.w;
+                }
+#pragma unroll
+                for (int i = 4 * NQ; i < L; ++i) w[i] = ((const uint32_t *)p)[i];
+#pragma unroll
+                for (int i = 0; i < L; ++i) {
+                    xr[i] = (double)(int16_t)(w[i] & 65535u) * 0x1p-15;
+                    xi[i] = (double)((int32_t)w[i] >> 16) * 0x1p-15;
                 }
             } break;
             default: {

@@ -177,6 +177,7 @@ void run_ref(BE &be, const RefPlanHost &h, int rows, int fmt, const RefBuffers &
     case FMT_CU8: sh ? run_ref_fmt<BE, FMT_CU8, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CU8, false>(be, h, rows, B, io); break;
     case FMT_CS8: sh ? run_ref_fmt<BE, FMT_CS8, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CS8, false>(be, h, rows, B, io); break;
     case FMT_CF32: sh ? run_ref_fmt<BE, FMT_CF32, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CF32, false>(be, h, rows, B, io); break;
+    case FMT_CS16: sh ? run_ref_fmt<BE, FMT_CS16, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CS16, false>(be, h, rows, B, io); break;
     default: sh ? run_ref_fmt<BE, FMT_CF64, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CF64, false>(be, h, rows, B, io); break;
     }
 }

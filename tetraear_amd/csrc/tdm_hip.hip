@@ -649,8 +649,8 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
     return TDM_OK;
 }
 
-static size_t fmt_bytes(int fmt) { return fmt == TDM_CU8 || fmt == TDM_CS8 ? 2 : (fmt == TDM_CF32 ? 8 : 16); }
-static int tetra_fmt8(int fmt) { return fmt == TDM_CU8 ? 1 : (fmt == TDM_CS8 ? 2 : 0); }   // the TETRA-mode kernels' FMT8
+static size_t fmt_bytes(int fmt) { return fmt == TDM_CU8 || fmt == TDM_CS8 ? 2 : (fmt == TDM_CS16 ? 4 : (fmt == TDM_CF32 ? 8 : 16)); }
+static int tetra_fmt8(int fmt) { return fmt == TDM_CU8 ? 1 : (fmt == TDM_CS8 ? 2 : (fmt == TDM_CS16 ? 3 : 0)); }   // the TETRA-mode kernels' FMT8
 
 // Geometry of a chunk walked in K pieces (oracle/tetra_np.py gardner_segments is the same arithmetic): false when the chunk is
 // too short (a piece's own part, n / K, under 1.9 warm-ups)
@@ -795,7 +795,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
     if (!out) return fail(TDM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!(sample_rate > 0) || n_samples < 1 || n_samples > (int64_t(1) << 31) || n_carriers < 1 || n_carriers > 65535 ||
-        in_fmt < 0 || in_fmt > 3)
+        in_fmt < 0 || in_fmt > TDM_CS16)
         return fail(TDM_ERR_INVALID, "bad sample_rate / n_samples / n_carriers (1..65535) / in_fmt");
     if (mode != TDM_MODE_REFERENCE && mode != TDM_MODE_TETRA && mode != TDM_MODE_TETRA_GARDNER) return fail(TDM_ERR_INVALID, "bad mode");
     int rc = use_device(device);
@@ -809,7 +809,8 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
         // channelised baseband in: sample_rate is the per-carrier rate, >= 2 samples per symbol
         // channelised baseband as cf32 (the channeliser's output), or straight off the wire as cu8 / cs8 (round 6: converted where
         // the kernels stage their window; one bf16 plane per component in the fused receiver)
-        if (in_fmt == TDM_CF64) return fail(TDM_ERR_UNSUPPORTED, "TETRA mode takes cf32, cu8 or cs8 baseband");
+        // (cs16: packed like the bytes, but staged as the cf32 values it means -- the cf32 arithmetic behind the loader)
+        if (in_fmt == TDM_CF64) return fail(TDM_ERR_UNSUPPORTED, "TETRA mode takes cf32, cu8, cs8 or cs16 baseband");
         const double sps = sample_rate / kSymbolRate;
         if (sps < 2.0 || sps > 8.0) return fail(TDM_ERR_UNSUPPORTED, "TETRA mode needs 2..8 samples per symbol");
         if (n_samples < 64 || n_samples > (int64_t)kMaxTimingBlocks * kTimingBlock)
@@ -871,8 +872,8 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
         if (mode == TDM_MODE_TETRA_GARDNER) {
             p->rows = n_carriers;
             p->device = device;
-            // (8-bit input: the fused kernel is instantiated for 33 and 35 taps; other tap counts take the three launches, whose
-            //  matched filter converts)
+            // (8-bit input: the fused kernel is instantiated for 33 and 35 taps; other tap counts, and cs16 at every tap count,
+            //  take the three launches, whose matched filter converts)
             p->gardner_fused_ok = (debug_value("gardner_fused") != 0 && tetra_gardner_fused_available(tp.ntaps, n_carriers, tetra_fmt8(in_fmt))) ? 1 : 0;
             p->gardner_ntaps_design = ntaps_design;
             {
@@ -1367,7 +1368,8 @@ int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int
     if (depth < 1 || depth > 16) return fail(TDM_ERR_INVALID, "tdm_stream_create: depth 1..16");
     if (!(sample_rate > 0) || n_samples < 1 || n_samples > (int64_t(1) << 31) || n_rows < 1 || n_rows > 65535)
         return fail(TDM_ERR_INVALID, "tdm_stream_create: bad sample_rate / n_samples / n_rows (1..65535)");
-    if (in_fmt < 0 || in_fmt > 3) return fail(TDM_ERR_INVALID, "tdm_stream_create: bad in_fmt");
+    // (cs16 is not taken here yet: the host-fed stream's slots are sized and checked for the four formats below)
+    if (in_fmt < 0 || in_fmt > TDM_CF64) return fail(TDM_ERR_INVALID, "tdm_stream_create: bad in_fmt (cu8, cs8, cf32 or cf64)");
     if (mode != TDM_MODE_REFERENCE && mode != TDM_MODE_TETRA && mode != TDM_MODE_TETRA_GARDNER)
         return fail(TDM_ERR_INVALID, "tdm_stream_create: bad mode");
     if (flags & ~TDM_STREAM_SOFT) return fail(TDM_ERR_INVALID, "tdm_stream_create: unknown flags");
@@ -2229,7 +2231,7 @@ int tdm_resample(const double *x, int64_t n, int64_t num, double *y, int32_t dev
 int tdm_spectrum_gate(const void *iq, int32_t in_fmt, int64_t row_stride, int64_t n_samples, int32_t rows,
                       double sample_rate, double *out, double *afc, int32_t device_pointers, int32_t device)
 {
-    if (!iq || !out || rows < 1 || n_samples < 0 || in_fmt < 0 || in_fmt > 3 || !(sample_rate > 0))
+    if (!iq || !out || rows < 1 || n_samples < 0 || in_fmt < 0 || in_fmt > TDM_CS16 || !(sample_rate > 0))
         return fail(TDM_ERR_INVALID, "bad argument");
     int rc = use_device(device);
     if (rc) return rc;
@@ -2552,12 +2554,14 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
                     switch (fmt) {
                     case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS, true>; break;
                     case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS, true>; break;
+                    case TDM_CS16: kern = one ? k_pfb_fft<M1, M2, P, TB, 4, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 4, 2, WGS, true>; break;
                     default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS, true>; break;
                     }
                 } else {
                     switch (fmt) {
                     case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS, false>; break;
                     case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS, false>; break;
+                    case TDM_CS16: kern = one ? k_pfb_fft<M1, M2, P, TB, 4, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 4, 2, WGS, false>; break;
                     default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS, false>; break;
                     }
                 }
@@ -2640,7 +2644,7 @@ int tdm_channelise_batch(const void *iq, int32_t in_fmt, int64_t n_in, int32_t n
 {
     if (!iq || !out || !n_out || n_in < 1 || D < 1 || n_streams < 1 || n_streams > 65535 ||
         (out_pitch != 0 && out_pitch < (n_in + D - 1) / D) ||
-        (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32))
+        (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32 && in_fmt != TDM_CS16))
         return fail(TDM_ERR_INVALID, "bad argument");
     int rc = use_device(device);
     if (rc) return rc;
@@ -2763,8 +2767,8 @@ int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_strea
     // every refusal before the first HIP call
     if (!out) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: out is null");
     *out = nullptr;
-    if (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32)
-        return fail(TDM_ERR_INVALID, "tdm_channeliser_create: in_fmt must be cu8, cs8 or cf32");
+    if (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32 && in_fmt != TDM_CS16)
+        return fail(TDM_ERR_INVALID, "tdm_channeliser_create: in_fmt must be cu8, cs8, cs16 or cf32");
     if (D < 1) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: decimation D < 1");
     if (n_streams < 1 || n_streams > 65535) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: n_streams 1..65535");
     if (max_n_in < 1 || max_n_in > (int64_t(1) << 40) / n_streams)
@@ -2838,6 +2842,9 @@ int tdm_channeliser_push(tdm_channeliser *ch, const void *iq, int64_t n_in, floa
     if (ch->fmt == TDM_CF32)
         hipLaunchKernelGGL(k_pfb_hist<uint2>, hgrid, dim3(256), 0, st, (const uint2 *)src, n_in, (const uint2 *)ch->hist[ch->cur].get(),
                            (uint2 *)ch->hist[ch->cur ^ 1].get(), ch->hist_stride / fb, n_in, ch->L);
+    else if (ch->fmt == TDM_CS16)
+        hipLaunchKernelGGL(k_pfb_hist<uint32_t>, hgrid, dim3(256), 0, st, (const uint32_t *)src, n_in,
+                           (const uint32_t *)ch->hist[ch->cur].get(), (uint32_t *)ch->hist[ch->cur ^ 1].get(), ch->hist_stride / fb, n_in, ch->L);
     else
         hipLaunchKernelGGL(k_pfb_hist<uint16_t>, hgrid, dim3(256), 0, st, (const uint16_t *)src, n_in,
                            (const uint16_t *)ch->hist[ch->cur].get(), (uint16_t *)ch->hist[ch->cur ^ 1].get(), ch->hist_stride / fb, n_in, ch->L);

@@ -25,6 +25,7 @@ void launch_zp_block(const ZpParams &P, const Loader &ld, int nb, int rows, hipS
 #define TDM_ZP_DEC(FMT, SH) template void launch_zp_block<2, 4, kLDec, kEdgeSos, RawLoader<FMT, SH>>(const ZpParams &, const RawLoader<FMT, SH> &, int, int, hipStream_t);
 TDM_ZP_DEC(FMT_CU8, false) TDM_ZP_DEC(FMT_CU8, true) TDM_ZP_DEC(FMT_CS8, false) TDM_ZP_DEC(FMT_CS8, true)
 TDM_ZP_DEC(FMT_CF32, false) TDM_ZP_DEC(FMT_CF32, true) TDM_ZP_DEC(FMT_CF64, false) TDM_ZP_DEC(FMT_CF64, true)
+TDM_ZP_DEC(FMT_CS16, false) TDM_ZP_DEC(FMT_CS16, true)
 #undef TDM_ZP_DEC
 template void launch_zp_block<2, 2, kLLpf, kEdgeTf, StagedLoader<DecFixSrc<kLDec>>>(const ZpParams &, const StagedLoader<DecFixSrc<kLDec>> &, int, int, hipStream_t);
 template void launch_zp_block<2, 2, kLLpf, kEdgeTf, StagedLoader<PlainC128Src>>(const ZpParams &, const StagedLoader<PlainC128Src> &, int, int, hipStream_t);

@@ -16,6 +16,7 @@ bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int6
 #define TDM_RRC_CASE(NT) case NT:                                                      \
         if (fmt8 == 1) hipLaunchKernelGGL((k_tetra_fused<NT, 1>), TDM_RRC_ARGS);         \
         else if (fmt8 == 2) hipLaunchKernelGGL((k_tetra_fused<NT, 2>), TDM_RRC_ARGS);    \
+        else if (fmt8 == 3) hipLaunchKernelGGL((k_tetra_fused<NT, 3>), TDM_RRC_ARGS);    \
         else hipLaunchKernelGGL((k_tetra_fused<NT, 0>), TDM_RRC_ARGS);                   \
         return true;
         TDM_RRC_CASE(17) TDM_RRC_CASE(25) TDM_RRC_CASE(33) TDM_RRC_CASE(35) TDM_RRC_CASE(41) TDM_RRC_CASE(49) TDM_RRC_CASE(57) TDM_RRC_CASE(65)
@@ -33,6 +34,7 @@ bool tetra_mf_launch(const TetraParams &tp, int rows, const void *x, int fmt8, i
 #define TDM_MF_CASE(NT) case NT:                                                                                                             \
         if (fmt8 == 1) hipLaunchKernelGGL((k_tetra_mf<NT, 1>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);              \
         else if (fmt8 == 2) hipLaunchKernelGGL((k_tetra_mf<NT, 2>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);         \
+        else if (fmt8 == 3) hipLaunchKernelGGL((k_tetra_mf<NT, 3>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);         \
         else hipLaunchKernelGGL((k_tetra_mf<NT, 0>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);                        \
         return true;
         TDM_MF_CASE(17) TDM_MF_CASE(25) TDM_MF_CASE(33) TDM_MF_CASE(35) TDM_MF_CASE(41) TDM_MF_CASE(49) TDM_MF_CASE(57) TDM_MF_CASE(65)
@@ -78,6 +80,7 @@ bool tetra_gardner_fused_available(int ntaps, int rows, int fmt8)
 {
     const void *fn = gardner_fused_kernel(ntaps);
     if (!fn) return false;
+    if (fmt8 == 3) return false;                            // (cs16: no fused instantiation, the three launches)
     if (fmt8 && ntaps != 33 && ntaps != 35) return false;   // (tetra_gardner_fused_launch: the 8-bit instantiations)
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return true;
@@ -100,6 +103,7 @@ bool tetra_gardner_fused_launch(const TetraParams &tp, int rows, const void *x_,
     const GardnerConsts G = gardner_gains();
     const dim3 grid((unsigned)((rows + kGQuads - 1) / kGQuads)), block(64 * kGWaves);
     const float2 *x = (const float2 *)x_;
+    if (fmt8 == 3) return false;   // (cs16 takes the three launches: tetra_gardner_fused_available)
     if (fmt8) {   // 8-bit input: the tap counts of 4 and 4.44 samples per symbol (72 / 80 kS/s) -- the others take the three launches
         switch (tp.ntaps) {
 #define TDM_GF8_CASE(NT) case NT:                                                                                                                  \

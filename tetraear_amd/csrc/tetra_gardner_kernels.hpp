@@ -76,6 +76,9 @@ __device__ __forceinline__ float2 mf_convert8(uint32_t h)   // low 16 bits: I, Q
     return make_float2((float)(int8_t)(h & 255u) * (1.f / 128.f), (float)(int8_t)((h >> 8) & 255u) * (1.f / 128.f));
 }
 
+// FMT8 == 3: cs16 (one 4-byte word per sample, s * 2^-15): pairs of samples as 8-byte loads where the whole window lies inside the
+// chunk and the pair address is 8-byte aligned, else one 4-byte load per sample from clamped positions; staged as the floats the cf32
+// call stages, so the output is that call's bit for bit.
 template <int NT, int FMT8 = 0>
 __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict__ x_, int64_t in_stride, const TetraParams P,
                                                          float2 *__restrict__ y, int64_t y_pitch)
@@ -90,6 +93,8 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
     const int row = blockIdx.y, tid = threadIdx.x, n = P.n;
     const float2 *xr = x + (int64_t)row * in_stride;
     const uint16_t *xr8 = (const uint16_t *)x_ + (int64_t)row * in_stride;   // (FMT8: one 2-byte sample per element)
+    const uint32_t *xr16 = (const uint32_t *)x_ + (int64_t)row * in_stride;  // (cs16: one 4-byte sample per element)
+    constexpr bool K8 = FMT8 == 1 || FMT8 == 2, K16 = FMT8 == 3;
     float2 *yr = y + (int64_t)row * y_pitch;
     // a workgroup walks kMfTilesPerWg consecutive tiles with the NEXT tile's window already on its way from HBM while it
     // works on the current one: the memory pipes never wait for a workgroup's arithmetic phase
@@ -102,8 +107,30 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
     f32x4 vp[NLP];
     auto interior = [&](int base) { return base - H >= 0 && base - H + W <= n; };
     uint32_t v8[NLD];   // (FMT8) the thread's samples of the window as they arrive
+    typedef uint32_t u32pair __attribute__((ext_vector_type(2)));
+    u32pair v16[NLP];   // (cs16) pairs of the window, or its single samples two to a register pair
+    auto pairs16 = [&](int base) { return interior(base) && (((uintptr_t)(xr16 + (base - H))) & 7) == 0; };
     auto fetch = [&](int base) {
-        if (FMT8) {
+        if (K16) {
+            if (pairs16(base)) {
+                const u32pair *pb = (const u32pair *)(xr16 + (base - H));
+#pragma unroll
+                for (int k = 0; k < NLP; ++k) {
+                    const int pi = tid + k * kMfThreads;
+                    if (k < NLP - 1 || pi < W / 2) v16[k] = __builtin_nontemporal_load(pb + pi);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < NLD; ++k) {
+                    const int g = base - H + tid + k * kMfThreads;
+                    const uint32_t q = xr16[min(max(g, 0), n - 1)];
+                    if (k & 1) v16[k >> 1].y = q;
+                    else v16[k >> 1].x = q;
+                }
+            }
+            return;
+        }
+        if (K8) {
 #pragma unroll
             for (int k = 0; k < NLD; ++k) {
                 const int g = base - H + tid + k * kMfThreads;
@@ -129,7 +156,27 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
         }
     };
     auto stage = [&](int base) {
-        if (FMT8) {
+        if (K16) {
+            if (pairs16(base)) {
+#pragma unroll
+                for (int k = 0; k < NLP; ++k) {
+                    const int pi = tid + k * kMfThreads;
+                    if (k < NLP - 1 || pi < W / 2) {
+                        const float2 a = tetra_conv16(v16[k].x), b = tetra_conv16(v16[k].y);
+                        *(f32x4 *)(xs + slot(2 * pi)) = f32x4{a.x, a.y, b.x, b.y};
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < NLD; ++k) {
+                    const int i = tid + k * kMfThreads, g = base - H + i;
+                    const uint32_t q = (k & 1) ? v16[k >> 1].y : v16[k >> 1].x;
+                    if (i < W) xs[slot(i)] = (g >= 0 && g < n) ? tetra_conv16(q) : make_float2(0.f, 0.f);
+                }
+            }
+            return;
+        }
+        if (K8) {
 #pragma unroll
             for (int k = 0; k < NLD; ++k) {
                 const int i = tid + k * kMfThreads, g = base - H + i;

@@ -169,6 +169,9 @@ struct TetraIn8 {
     }
 };
 
+// FMT8 == 3: cs16, int16 I then int16 Q, one 4-byte word per sample.  PACKED input like the 8-bit formats (converted where the
+// window is staged: s * 2^-15, exact in fp32), but NOT one bf16 plane: a 16-bit integer needs the leading and the trailing bf16
+// (their sum is the sample exactly), so behind the staging it is the cf32 kernel -- four planes, four products, no scale at the store.
 template <int NT, int FMT8 = 0>
 __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fused(const void *__restrict__ x_, int64_t in_stride,
                                                               const TetraParams P, float2 *__restrict__ soft,
@@ -179,6 +182,8 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     static_assert(kRrcPerThread == 8 && kRrcThreads % 64 == 0 && kTimingBlock == 256, "a wavefront owns two timing sub-blocks of a tile");
     static_assert(kRing % kTimingBlock == 0 && kRing - kRrcTile - kTimingBlock * (2 * kTimingHalfWin + 1) / 2 >= kTimingBlock / 2, "ring too short");
     constexpr int PER = kRrcPerThread;
+    constexpr bool K8 = FMT8 == 1 || FMT8 == 2;   // 8-bit input: one bf16 plane per component, the format's scale at the store
+    constexpr bool K16 = FMT8 == 3;               // cs16: packed input, cf32 arithmetic
     constexpr int HALO = NT - 1, H2 = HALO / 2;
     constexpr int KS = (kRrcRun + HALO + 31) / 32;        // matrix-core steps (32 window positions each) per run of 16 outputs
     constexpr int NS = kRrcTile - kRrcRun + 32 * KS;      // samples staged per tile: base - H2 .. base - H2 + NS
@@ -211,6 +216,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     const double sps = P.sps;
     const float2 *xr = (const float2 *)x_ + (int64_t)row * in_stride;     // rows of the channeliser may carry a pitch
     const uint16_t *xr8 = (const uint16_t *)x_ + (int64_t)row * in_stride;   // (FMT8: one 2-byte sample per element)
+    const uint32_t *xr16 = (const uint32_t *)x_ + (int64_t)row * in_stride;  // (cs16: one 4-byte sample per element)
     float2 *sr = soft + (int64_t)row * P.max_soft;
     const int nb = (n + kTimingBlock - 1) / kTimingBlock;
     const int ntiles = (n + kRrcTile - 1) / kRrcTile;
@@ -232,9 +238,29 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     const float2 x_first = FMT8 ? make_float2(0.f, 0.f) : xr[0], x_last = FMT8 ? make_float2(0.f, 0.f) : xr[n - 1];
     f32x4 pf[NP];
     uint32_t pf8[NP];   // (FMT8) a pair of consecutive samples as it arrives: low half the first
+    typedef uint32_t u32pair __attribute__((ext_vector_type(2)));
+    u32pair pf16[NP];   // (cs16) a pair of consecutive samples as it arrives
     auto fetch = [&](int tile) {
         const int g0 = tile * kRrcTile - H2;
-        if (FMT8) {
+        if (K16) {
+            if (g0 >= 0 && g0 + 2 * (NP * kRrcThreads - 1) + 1 <= n - 1 && (((uintptr_t)(xr16 + g0)) & 7) == 0) {
+                // an inner tile whose pairs are 8-byte aligned: one load per pair
+                const u32pair *pb = (const u32pair *)(xr16 + g0);
+#pragma unroll
+                for (int j = 0; j < NP - 1; ++j) pf16[j] = __builtin_nontemporal_load(pb + tid + j * kRrcThreads);
+                if (last_turn) pf16[NP - 1] = __builtin_nontemporal_load(pb + tid + (NP - 1) * kRrcThreads);
+                return;
+            }
+            // else two 4-byte loads per pair from clamped positions (rows are 4-byte aligned and no more); stage() masks
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                if (j == NP - 1 && !last_turn) break;
+                const int g = g0 + 2 * (tid + j * kRrcThreads);
+                pf16[j] = u32pair{xr16[min(max(g, 0), n - 1)], xr16[min(max(g + 1, 0), n - 1)]};
+            }
+            return;
+        }
+        if (K8) {
             if (g0 >= 0 && g0 + 2 * (NP * kRrcThreads - 1) + 1 <= n - 1 && (((uintptr_t)(xr8 + g0)) & 3) == 0) {
                 // an inner tile whose pairs are 4-byte aligned: one load per pair
                 const uint32_t *pb = (const uint32_t *)(xr8 + g0);
@@ -280,7 +306,18 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     };
     auto stage = [&](int tile) __attribute__((always_inline)) {
         const int g0 = tile * kRrcTile - H2;       // chunk position of the first pair
-        if (FMT8) {
+        if (K16) {   // the values the cf32 call stages, through the same split
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                if (j == NP - 1 && !last_turn) break;
+                const int idx = tid + j * kRrcThreads, g = g0 + 2 * idx;
+                const float2 e0 = (g >= 0 && g < n) ? tetra_conv16(pf16[j].x) : make_float2(0.f, 0.f);
+                const float2 e1 = (g + 1 >= 0 && g + 1 < n) ? tetra_conv16(pf16[j].y) : make_float2(0.f, 0.f);
+                put(idx, j == NP - 1, e0.x, e0.y, e1.x, e1.y);
+            }
+            return;
+        }
+        if (K8) {
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
                 if (j == NP - 1 && !last_turn) break;
@@ -433,7 +470,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
                 const bf16x8 r1 = __builtin_bit_cast(bf16x8, ab[o]), r2 = __builtin_bit_cast(bf16x8, ab[PLANE / 4 + o]);
                 const bf16x8 i1 = __builtin_bit_cast(bf16x8, ab[2 * (PLANE / 4) + o]), i2 = __builtin_bit_cast(bf16x8, ab[3 * (PLANE / 4) + o]);
                 const bf16x8 h1 = __builtin_bit_cast(bf16x8, hB1[s]), h2 = __builtin_bit_cast(bf16x8, hB2[s]);
-                if (!FMT8) {   // (8-bit input: no trailing halves)
+                if (!K8) {   // (8-bit input: no trailing halves)
                     cre[bb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(r2, h2, cre[bb], 0, 0, 0);   // (smallest terms first)
                     cim[bb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(i2, h2, cim[bb], 0, 0, 0);
                     cre[bb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(r2, h1, cre[bb], 0, 0, 0);
@@ -659,7 +696,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
             for (int u = 0; u < SU; ++u)
                 if (kb + off + u * TSYM < k_end) {
                     float2 sv = farrow_eval(f[u]);
-                    if (FMT8) { sv.x *= TetraIn8<FMT8>::scale; sv.y *= TetraIn8<FMT8>::scale; }
+                    if (K8) { sv.x *= TetraIn8<FMT8>::scale; sv.y *= TetraIn8<FMT8>::scale; }
                     so[off + u * TSYM] = sv;
                     amax = fmaxf(amax, fmaxf(fabsf(sv.x), fabsf(sv.y)));
                 }
@@ -685,7 +722,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
                     for (int k2 = -3; k2 < NT; ++k2) {
                         const int idx = first + k2 + 3;
                         float2 q3 = make_float2(0.f, 0.f);
-                        if (idx >= 0 && idx < n) q3 = FMT8 ? TetraIn8<FMT8>::conv(xr8[idx]) : xr[idx];
+                        if (idx >= 0 && idx < n) q3 = K8 ? TetraIn8<FMT8>::conv(xr8[idx]) : (K16 ? tetra_conv16(xr16[idx]) : xr[idx]);
                         if (k2 >= 0) {   // tap k2 multiplies x[first + k2 + e] for output e
                             const float h = P.taps[k2];
                             a0x = fmaf(h, q0.x, a0x); a0y = fmaf(h, q0.y, a0y);
@@ -702,7 +739,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
                     f.y1 = make_float2(a2x, a2y);
                     f.y2 = make_float2(a3x, a3y);
                     float2 sv = farrow_eval(f);
-                    if (FMT8) { sv.x *= TetraIn8<FMT8>::scale; sv.y *= TetraIn8<FMT8>::scale; }
+                    if (K8) { sv.x *= TetraIn8<FMT8>::scale; sv.y *= TetraIn8<FMT8>::scale; }
                     sr[k - k_lo] = sv;
                     amax = fmaxf(amax, fmaxf(fabsf(sv.x), fabsf(sv.y)));
                 }

@@ -9,6 +9,11 @@
 namespace tdm {
 
 constexpr int kRrcMaxTaps = 96;
+// a cs16 sample (one word: int16 I in the low half, int16 Q in the high) as the value it means, s / 32768: exact in fp32
+__device__ __forceinline__ float2 tetra_conv16(uint32_t w)
+{
+    return make_float2((float)(int16_t)(w & 65535u) * 0x1p-15f, (float)((int32_t)w >> 16) * 0x1p-15f);
+}
 #define TDM_TETRA_THREADS 256
 constexpr int kRrcThreads = TDM_TETRA_THREADS;            // 256: three workgroups per CU fit in LDS (0.465 ms per 4096 x 32768); 512: two (0.48 ms)
 #define TDM_TETRA_PER 8
@@ -47,14 +52,14 @@ struct TetraParams {
 // one launch of the fused receiver on `rows` carriers; returns false when no kernel is instantiated for tp.ntaps
 // row_list / n_rows (device, or null): the launch covers the rows listed -- workgroup i takes row row_list[i], workgroups
 // past *n_rows leave at once -- instead of all `rows`
-// fmt8: 0 cf32 input, 1 cu8, 2 cs8 (tetra_kernels.hpp TetraIn8)
+// fmt8: 0 cf32 input, 1 cu8, 2 cs8 (tetra_kernels.hpp TetraIn8), 3 cs16 (packed input, the cf32 arithmetic)
 bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *soft, uint8_t *hard,
                   int32_t *n_soft, int32_t *timing_milli, double *min_margin, hipStream_t stream, const int32_t *row_list = nullptr,
                   const int32_t *n_rows = nullptr);
 
 // TDM_MODE_TETRA_GARDNER (tetra_gardner_kernels.hpp): the three launches, each on its own so that the caller can time them.
 // y: [rows][y_pitch] cf32 matched-filter output (y_pitch even, >= tp.n); false when no kernel is instantiated for tp.ntaps
-// fmt8: 0 cf32 input, 1 cu8, 2 cs8 (converted where the window is staged)
+// fmt8: 0 cf32 input, 1 cu8, 2 cs8, 3 cs16 (converted where the window is staged)
 bool tetra_mf_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *y, int64_t y_pitch, hipStream_t stream);
 void tetra_gardner_loop_launch(const TetraParams &tp, int rows, const float2 *y, int64_t y_pitch, float2 *soft, int32_t *n_soft,
                                int32_t *timing_milli, hipStream_t stream);

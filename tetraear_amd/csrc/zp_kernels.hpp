@@ -195,7 +195,7 @@ typedef NcoRunT<kWave> NcoRun;   // a lane of the staged loader visits j, j + 64
 // ------------------------------------------------------------------------------------------
 // Loaders: give a lane its L consecutive samples of the padded, odd-extended signal.
 // ------------------------------------------------------------------------------------------
-enum { FMT_CU8 = 0, FMT_CS8 = 1, FMT_CF32 = 2, FMT_CF64 = 3 };
+enum { FMT_CU8 = 0, FMT_CS8 = 1, FMT_CF32 = 2, FMT_CF64 = 3, FMT_CS16 = 4 };
 
 template <int FMT>
 TDM_HD void convert_one(const void *rowp, int64_t k, double &re, double &im)
@@ -215,6 +215,10 @@ TDM_HD void convert_one(const void *rowp, int64_t k, double &re, double &im)
         const float *p = (const float *)rowp + 2 * k;
         re = (double)p[0];
         im = (double)p[1];
+    } else if (FMT == FMT_CS16) {
+        const int16_t *p = (const int16_t *)rowp + 2 * k;   // s / 32768, exact
+        re = (double)p[0] * 0x1p-15;
+        im = (double)p[1] * 0x1p-15;
     } else {
         const double *p = (const double *)rowp + 2 * k;
         re = p[0];
@@ -230,7 +234,7 @@ struct RawLoader {
     double fs;
     int32_t rows_per_chunk;    // > 1: that many consecutive plan rows read the same input row (RawLoaderRT::rows_per_chunk)
 
-    static constexpr int kBytes = (FMT == FMT_CU8 || FMT == FMT_CS8) ? 2 : (FMT == FMT_CF32 ? 8 : 16);
+    static constexpr int kBytes = (FMT == FMT_CU8 || FMT == FMT_CS8) ? 2 : (FMT == FMT_CS16 ? 4 : (FMT == FMT_CF32 ? 8 : 16));
     static constexpr bool kStaged = false;  // lanes load their own segment straight from memory
 
     TDM_HD const void *row_ptr(int row) const
@@ -270,6 +274,18 @@ struct RawLoader {
                             xi[idx] = (double)(int8_t)((s >> 8) & 255u) * (1.0 / 128.0);
                         }
                     }
+            }
+        } else if (FMT == FMT_CS16 && aligned && L % 4 == 0) {
+            const u32x4 *v = (const u32x4 *)p;   // 16 bytes = 4 samples: int16 I in the low half of a word, Q in the high
+#pragma unroll
+            for (int c = 0; c < L / 4; ++c) {
+                const u32x4 w = v[c];
+                const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    xr[c * 4 + d] = (double)(int16_t)(ww[d] & 65535u) * 0x1p-15;
+                    xi[c * 4 + d] = (double)((int32_t)ww[d] >> 16) * 0x1p-15;
+                }
             }
         } else if (FMT == FMT_CF64 && aligned) {
             const f64x2 *v = (const f64x2 *)p;

@@ -5,7 +5,7 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import FMT_BYTES, check, ptr
 
-_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cf64": 3}
+_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cf64": 3, "cs16": 4}
 FIELDS = ("peak_freq_offset", "signal_power", "peak_power", "noise_floor", "snr", "strong", "afc")
 
 

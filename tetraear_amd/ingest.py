@@ -247,7 +247,7 @@ def _iter_overlapped(source, sample_rate, chunk, freq_offset, rows_per_batch, de
 
 def iter_channels(source, M, D, chunk, fmt="cu8", streams=1, device=0):
     """source: path of a wideband IQ file, an object with readinto() (open file, pipe), or an array of its bytes, in the wire
-    format `fmt` (cu8 / cs8 / cf32).  Each read takes `streams` x `chunk` samples, the streams back to back ([streams][chunk]),
+    format `fmt` (cu8 / cs8 / cs16 / cf32).  Each read takes `streams` x `chunk` samples, the streams back to back ([streams][chunk]),
     and yields that read's channel block, complex64 [streams][M][n_out] -- the last, shorter read as it is (its bytes split
     evenly between the streams).  The blocks go through one StreamingChanneliser, so concatenated along time they equal one
     channelise_batch call over the whole source; n_out varies from read to read (ceil / floor of chunk / D) and may be 0."""

@@ -14,7 +14,7 @@ from collections import OrderedDict
 import numpy as np
 
 from tetraear_amd import _lib
-from tetraear_amd._lib import FMT_CF32, FMT_CF64, FMT_CU8, check, ptr
+from tetraear_amd._lib import FMT_CF32, FMT_CF64, FMT_CS16, FMT_CU8, check, ptr
 from tetraear_amd.batch import BatchDemodulator
 
 logger = logging.getLogger(__name__)
@@ -166,6 +166,16 @@ class SignalProcessor:
             self.symbols = np.array([], dtype=complex)
             return np.array([], dtype=np.uint8)
         return self._run(u8, FMT_CU8, n, freq_offset)
+
+    def process_cs16(self, iq_int16, freq_offset=0):
+        """process() fed with the interleaved int16 I,Q of a 16-bit radio (sc16 / CS16) instead of the complex128 array
+        s / 32768 made from them; identical results, 4x less host->device traffic."""
+        s16 = np.ascontiguousarray(iq_int16, dtype=np.int16)
+        n = len(s16) // 2
+        if n == 0:
+            self.symbols = np.array([], dtype=complex)
+            return np.array([], dtype=np.uint8)
+        return self._run(s16, FMT_CS16, n, freq_offset)
 
     def _run(self, x, fmt, n, freq_offset):
         plan = _shared_plan(self.device, self.sample_rate, n, fmt)

@@ -14,7 +14,7 @@ from ._lib import FMT_BYTES, MODE_TETRA, check
 from .batch import BatchDemodulator, DeviceBuffer
 from .channeliser import aligned_pitch
 
-_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2}
+_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cs16": 4}
 
 
 class WidebandReceiver:
