@@ -7,11 +7,8 @@ I and Q content, so a swapped pair or swapped bytes cannot pass:
   2  values in {-1, 0, 1} only (low byte / sign extension)
   3  I at 0x0100 scale, Q at 0x0001 scale (byte order)
 """
-import ctypes as C
-
 import numpy as np
 
-FMT_CS16 = 4
 KINDS = 4
 
 
@@ -59,38 +56,3 @@ def quantise(x, scale=0.5):
     out[0::2] = np.clip(np.rint(32768 * x.real), -32768, 32767)
     out[1::2] = np.clip(np.rint(32768 * x.imag), -32768, 32767)
     return out
-
-
-def emu_process(sample_rate, iq, fmt, n, rows=1, stride=None, pre_shift=None, freq_offset=None):
-    """tests/emul/emul.py process() with the wire format as its integer code (that module's name table stops at cf64; the
-    library passes the code straight into run_ref)"""
-    from tests.emul import emul
-    L = emul.lib()
-    L.emu_rows_per_chunk(1)
-    ms = C.c_int32()
-    L.emu_process(C.c_double(sample_rate), C.c_int64(n), rows, int(fmt), None, C.c_int64(0), None, None,
-                  None, None, None, None, None, C.byref(ms))
-    ms = ms.value
-    hard = np.zeros((rows, ms), dtype=np.uint8)
-    soft = np.zeros((rows, ms), dtype=np.complex128)
-    n_soft = np.zeros(rows, dtype=np.int32)
-    bp = np.zeros(rows, dtype=np.int32)
-    mm = np.zeros(rows, dtype=np.float64)
-    iq = np.ascontiguousarray(iq)
-    ps = None if pre_shift is None else np.ascontiguousarray(pre_shift, dtype=np.float64)
-    fo = None if freq_offset is None else np.ascontiguousarray(freq_offset, dtype=np.float64)
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    L.emu_process(C.c_double(sample_rate), C.c_int64(n), rows, int(fmt), vp(iq), C.c_int64(n if stride is None else stride),
-                  vp(ps), vp(fo), vp(hard), vp(soft), vp(n_soft), vp(bp), vp(mm), None)
-    return hard, soft, n_soft, bp, mm
-
-
-def emu_gate(iq, fmt, n, rows, fs):
-    from tests.emul import emul
-    L = emul.lib()
-    iq = np.ascontiguousarray(iq)
-    out = np.zeros((rows, 8))
-    afc = np.zeros(rows)
-    L.emu_gate(iq.ctypes.data_as(C.c_void_p), C.c_int64(n), rows, int(fmt), C.c_double(fs),
-               out.ctypes.data_as(C.c_void_p), afc.ctypes.data_as(C.c_void_p))
-    return out, afc

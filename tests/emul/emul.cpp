@@ -506,4 +506,22 @@ int emu_small_dft(int n, const float *in, float *out)
     }
     return 0;
 }
+
+// wire_format.hpp as the host compiler sees it (tests/test_wire_format_cpu.py): n packed samples (cu8 / cs8: 2 bytes each,
+// cs16: one 4-byte word) decoded to fp64 and to fp32, re and im interleaved; -1 for a format without integer codes
+int emu_wire_bytes(int fmt) { return wire_accepts(kWireAll, fmt) ? wire_bytes(fmt) : -1; }
+int emu_wire_decode(int fmt, const void *packed, int64_t n, double *out64, float *out32)
+{
+    if (!wire_accepts(kWireAll, fmt) || !wire_packed(fmt)) return -1;
+    wire_dispatch<wire_bit(FMT_CU8) | wire_bit(FMT_CS8) | wire_bit(FMT_CS16), FMT_CS16>(fmt, [&](auto F) {
+        constexpr int FMT = decltype(F)::value;
+        for (int64_t i = 0; i < n; ++i) {
+            const uint32_t w = wire_packed8(FMT) ? ((const uint16_t *)packed)[i] : ((const uint32_t *)packed)[i];
+            wire_f64<FMT>(w, out64[2 * i], out64[2 * i + 1]);
+            out32[2 * i] = wire_f32<FMT>(wire_code_i<FMT>(w));
+            out32[2 * i + 1] = wire_f32<FMT>(wire_code_q<FMT>(w));
+        }
+    });
+    return 0;
+}
 }

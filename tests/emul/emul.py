@@ -6,6 +6,8 @@ import subprocess
 
 import numpy as np
 
+from tetraear_amd._lib import WIRE_FORMATS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -18,7 +20,7 @@ def lib():
     return _LIB
 
 
-FMT = {"cu8": 0, "cs8": 1, "cf32": 2, "cf64": 3}
+FMT = {name: code for name, (code, _, _) in WIRE_FORMATS.items()}
 
 
 def process(sample_rate, iq, fmt, n, rows=1, stride=None, pre_shift=None, freq_offset=None, rows_per_chunk=1):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import cs16_cases as cc
+from tests.emul import emul
 
 SOFT_TOL = 1e-10          # the project's reference-mode bound (tests/test_wire_formats_gpu.py SOFT_TOL)
 FOFFS = np.array([-2750.0, -1171.875, 0.0, 613.5])
@@ -51,9 +52,9 @@ def _equal_all_five(a, b, what):
 def test_emul_cs16_rows_vs_oracle_and_equal_to_cf64(fs, n):
     s16 = cc.rows(n, 4, seed=1600 + n % 11)
     xs = cc.c128(s16)
-    got = cc.emu_process(fs, s16, cc.FMT_CS16, n, rows=4, freq_offset=FOFFS)
+    got = emul.process(fs, s16, "cs16", n, rows=4, freq_offset=FOFFS)
     _check_rows_vs_oracle(fs, xs, FOFFS, got, f"cs16 fs {fs} n {n}")
-    same = cc.emu_process(fs, xs, 3, n, rows=4, freq_offset=FOFFS)
+    same = emul.process(fs, xs, "cf64", n, rows=4, freq_offset=FOFFS)
     _equal_all_five(got, same, f"cs16 against cf64, fs {fs} n {n}")
 
 
@@ -65,9 +66,9 @@ def test_emul_cs16_shared_input_with_pre_shifts(fs):
     x = cc.c128(s16)
     shifts = np.array([-600000.0, -25000.0, 0.0, 37500.0, 412500.0])
     foffs = np.array([-2750.0, -1171.875, 0.0, 613.5, 2990.25])
-    got = cc.emu_process(fs, s16, cc.FMT_CS16, n, rows=5, stride=0, pre_shift=shifts, freq_offset=foffs)
+    got = emul.process(fs, s16, "cs16", n, rows=5, stride=0, pre_shift=shifts, freq_offset=foffs)
     _check_rows_vs_oracle(fs, x, foffs, got, f"cs16 shared fs {fs}", shifts=shifts)
-    same = cc.emu_process(fs, x, 3, n, rows=5, stride=0, pre_shift=shifts, freq_offset=foffs)
+    same = emul.process(fs, x, "cf64", n, rows=5, stride=0, pre_shift=shifts, freq_offset=foffs)
     _equal_all_five(got, same, f"cs16 shared against cf64, fs {fs}")
 
 
@@ -78,8 +79,8 @@ def test_emul_cs16_row_stride_of_n_plus_one(fs):
     s16 = cc.rows(n, 4, seed=1660)
     padded = np.full((4, 2 * (n + 1)), 0x7abc, dtype=np.int16)
     padded[:, :2 * n] = s16
-    got = cc.emu_process(fs, padded, cc.FMT_CS16, n, rows=4, stride=n + 1, freq_offset=FOFFS)
-    dense = cc.emu_process(fs, s16, cc.FMT_CS16, n, rows=4, freq_offset=FOFFS)
+    got = emul.process(fs, padded, "cs16", n, rows=4, stride=n + 1, freq_offset=FOFFS)
+    dense = emul.process(fs, s16, "cs16", n, rows=4, freq_offset=FOFFS)
     _equal_all_five(got, dense, f"stride n + 1, fs {fs}")
     _check_rows_vs_oracle(fs, cc.c128(s16), FOFFS, got, f"cs16 stride n + 1 fs {fs}")
 
@@ -87,18 +88,18 @@ def test_emul_cs16_row_stride_of_n_plus_one(fs):
 def test_emul_gate_cs16_equals_cf64():
     n, fs = 16384, 2.4e6
     s16 = cc.rows(n, 4, seed=1670)
-    out, afc = cc.emu_gate(s16, cc.FMT_CS16, n, 4, fs)
-    ref_out, ref_afc = cc.emu_gate(cc.c128(s16), 3, n, 4, fs)
+    out, afc = emul.gate(s16, "cs16", n, 4, fs)
+    ref_out, ref_afc = emul.gate(cc.c128(s16), "cf64", n, 4, fs)
     assert np.array_equal(out, ref_out) and np.array_equal(afc, ref_afc)
     assert np.all(np.isfinite(out)) and len(np.unique(out[:, 0])) == 4      # (the rows are different signals)
 
 
 def test_python_tables_and_header_know_cs16():
     from tetraear_amd import _lib, batch, channeliser, gate, stream, wideband
-    assert _lib.FMT_CS16 == 4 and _lib.FMT_BYTES[_lib.FMT_CS16] == 4
+    assert _lib.WIRE_FORMATS["cs16"][:2] == (4, 4) and _lib.FMT_CS16 == 4 and _lib.FMT_BYTES[_lib.FMT_CS16] == 4
     for mod in (batch, channeliser, wideband, gate):
-        assert mod._FMT_OF["cs16"] == 4, mod.__name__
-    assert "cs16" not in stream._FMT_OF      # (tdm_stream_create does not take it: include/tetrahip.h)
+        assert mod.ACCEPTS["cs16"] == 4, mod.__name__
+    assert "cs16" not in stream.ACCEPTS      # (tdm_stream_create does not take it: include/tetrahip.h)
     header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tetrahip.h")
     import re
     text = open(header).read()

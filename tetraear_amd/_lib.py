@@ -10,9 +10,19 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TETRAHIP_LIB", os.path.join(_HERE, "libtetrahip.so"))  # override: experiments only
 
-FMT_CU8, FMT_CS8, FMT_CF32, FMT_CF64, FMT_CS16 = 0, 1, 2, 3, 4
+# The IQ wire formats: name -> (code of include/tetrahip.h, bytes per sample, numpy dtype of a host view).  This is the
+# Python side's one table; the C++ side's is csrc/wire_format.hpp (tests/test_wire_format_cpu.py holds the two together).
+WIRE_FORMATS = {"cu8": (0, 2, "uint8"), "cs8": (1, 2, "int8"), "cf32": (2, 8, "complex64"), "cf64": (3, 16, "complex128"),
+                "cs16": (4, 4, "int16")}
+FMT_CU8, FMT_CS8, FMT_CF32, FMT_CF64, FMT_CS16 = (WIRE_FORMATS[k][0] for k in ("cu8", "cs8", "cf32", "cf64", "cs16"))
+FMT_BYTES = {code: nbytes for code, nbytes, _ in WIRE_FORMATS.values()}
+FMT_VIEW_DTYPE = {code: dtype for code, _, dtype in WIRE_FORMATS.values()}
 MODE_REFERENCE, MODE_TETRA, MODE_TETRA_GARDNER = 0, 1, 2
-FMT_BYTES = {FMT_CU8: 2, FMT_CS8: 2, FMT_CF32: 8, FMT_CF64: 16, FMT_CS16: 4}
+
+
+def wire_codes(*names):
+    """name -> code of the formats an entry point accepts (a subset of WIRE_FORMATS)"""
+    return {k: WIRE_FORMATS[k][0] for k in names}
 
 
 class TetraHipError(RuntimeError):

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from ._lib import FMT_BYTES, FMT_CF32, FMT_CF64, FMT_CS8, FMT_CS16, FMT_CU8, MODE_REFERENCE, PlanInfo, check, ptr
 
-_FMT_OF = {"cu8": FMT_CU8, "cs8": FMT_CS8, "cf32": FMT_CF32, "cf64": FMT_CF64, "cs16": FMT_CS16}
+ACCEPTS = _lib.wire_codes("cu8", "cs8", "cf32", "cf64", "cs16")
 
 
 class DeviceBuffer:
@@ -49,7 +49,7 @@ class BatchDemodulator:
 
     def __init__(self, sample_rate, n_samples, n_carriers=1, fmt="cu8", device=0, mode=MODE_REFERENCE):
         self.lib = _lib.load()
-        self.fmt = _FMT_OF[fmt] if isinstance(fmt, str) else int(fmt)
+        self.fmt = ACCEPTS[fmt] if isinstance(fmt, str) else int(fmt)
         self.device = device
         self.handle = None
         self._dev = None

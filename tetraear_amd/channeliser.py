@@ -11,12 +11,12 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import FMT_BYTES, check, ptr
 
-_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cs16": 4}
+ACCEPTS = _lib.wire_codes("cu8", "cs8", "cf32", "cs16")
 
 
 def channelise(iq, fmt, M, D, device=0):
     """One wideband stream -> complex64 [M][ceil(n/D)]; channel k is centred on k*fs/M."""
-    f = _FMT_OF[fmt]
+    f = ACCEPTS[fmt]
     iq = np.ascontiguousarray(iq)
     n_in = iq.nbytes // FMT_BYTES[f]
     n_out = (n_in + D - 1) // D
@@ -35,7 +35,7 @@ def aligned_pitch(n_out):
 def channelise_batch(iq, fmt, n_streams, M, D, device=0, pitch=0):
     """n_streams wideband streams back to back -> complex64 [n_streams][M][ceil(n/D)] in one launch
     (a view of a [n_streams][M][pitch] array when a row pitch is given)."""
-    f = _FMT_OF[fmt]
+    f = ACCEPTS[fmt]
     iq = np.ascontiguousarray(iq)
     n_in = iq.nbytes // FMT_BYTES[f] // n_streams
     n_out = (n_in + D - 1) // D
@@ -59,7 +59,7 @@ class StreamingChanneliser:
         self.lib = _lib.load()
         self.handle = None
         self.M, self.D, self.streams, self.max_n_in = int(M), int(D), int(streams), int(max_n_in)
-        self.fmt = _FMT_OF[fmt] if isinstance(fmt, str) else int(fmt)
+        self.fmt = ACCEPTS[fmt] if isinstance(fmt, str) else int(fmt)
         h = C.c_void_p()
         check(self.lib.tdm_channeliser_create(self.M, self.D, self.fmt, self.streams, self.max_n_in, int(device), C.byref(h)))
         self.handle = h

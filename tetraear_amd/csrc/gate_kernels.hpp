@@ -33,13 +33,7 @@ struct GateArgs {
 
 TDM_HD void gate_load(const void *rowp, int fmt, int64_t k, double &re, double &im)
 {
-    switch (fmt) {
-    case FMT_CU8: convert_one<FMT_CU8>(rowp, k, re, im); break;
-    case FMT_CS8: convert_one<FMT_CS8>(rowp, k, re, im); break;
-    case FMT_CF32: convert_one<FMT_CF32>(rowp, k, re, im); break;
-    case FMT_CS16: convert_one<FMT_CS16>(rowp, k, re, im); break;
-    default: convert_one<FMT_CF64>(rowp, k, re, im); break;
-    }
+    wire_dispatch(fmt, [&](auto F) TDM_WIRE_INLINE { convert_one<decltype(F)::value>(rowp, k, re, im); });
 }
 
 TDM_HD unsigned bitrev11(unsigned x)
@@ -67,8 +61,7 @@ TDM_HD void gate_body(const GateArgs &A, Comm &cm, int row)
         }
         return;
     }
-    const void *rowp = (const char *)A.iq + (int64_t)row * A.row_stride *
-                                                (A.fmt == FMT_CU8 || A.fmt == FMT_CS8 ? 2 : (A.fmt == FMT_CS16 ? 4 : (A.fmt == FMT_CF32 ? 8 : 16)));
+    const void *rowp = (const char *)A.iq + (int64_t)row * A.row_stride * wire_bytes(A.fmt);
     for (int i = tid; i < N; i += nt) {
         double re, im;
         gate_load(rowp, A.fmt, i, re, im);

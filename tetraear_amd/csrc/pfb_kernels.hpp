@@ -16,6 +16,7 @@
 
 #include "chan_stream.hpp"
 #include "small_dft.hpp"
+#include "wire_format.hpp"
 
 namespace tdm {
 
@@ -46,8 +47,6 @@ struct PfbParams {
     int32_t pad3_;
 };
 
-// the input format's bytes per sample
-__host__ __device__ constexpr int pfb_fmt_bytes(int fmt) { return fmt == 2 ? 8 : (fmt == 4 ? 4 : 2); }
 // one past the last history sample of stream y (local index n < 0 lives at byte n * fb from here, fb = the format's bytes per
 // sample), or nullptr
 template <int L>
@@ -59,15 +58,15 @@ __device__ __forceinline__ const char *pfb_hist_end(const PfbParams &Q, int y, i
 
 __device__ __forceinline__ float2 pfb_load(const void *iq, int fmt, int64_t n)
 {
-    if (fmt == 0) {  // cu8, pyrtlsdr scaling
+    if (fmt == FMT_CU8) {
         const uint8_t *p = (const uint8_t *)iq + 2 * n;
-        return make_float2((float)p[0] * (1.f / 127.5f) - 1.f, (float)p[1] * (1.f / 127.5f) - 1.f);
-    } else if (fmt == 1) {
+        return make_float2(wire_f32<FMT_CU8>(p[0]), wire_f32<FMT_CU8>(p[1]));
+    } else if (fmt == FMT_CS8) {
         const int8_t *p = (const int8_t *)iq + 2 * n;
-        return make_float2((float)p[0] * (1.f / 128.f), (float)p[1] * (1.f / 128.f));
-    } else if (fmt == 4) {  // cs16: s / 32768, exact
+        return make_float2(wire_f32<FMT_CS8>(p[0]), wire_f32<FMT_CS8>(p[1]));
+    } else if (fmt == FMT_CS16) {
         const int16_t *p = (const int16_t *)iq + 2 * n;
-        return make_float2((float)p[0] * 0x1p-15f, (float)p[1] * 0x1p-15f);
+        return make_float2(wire_f32<FMT_CS16>(p[0]), wire_f32<FMT_CS16>(p[1]));
     }
     return ((const float2 *)iq)[n];
 }
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(kPfbThreads) void k_pfb(const void *__restrict__ iq
     const int64_t m0 = (int64_t)blockIdx.x * T;
     iq = (const char *)iq + (int64_t)blockIdx.y * Q.in_stride;
     out += (int64_t)blockIdx.y * Q.out_batch;
-    const char *hend = pfb_hist_end<L>(Q, blockIdx.y, pfb_fmt_bytes(Q.fmt));
+    const char *hend = pfb_hist_end<L>(Q, blockIdx.y, wire_bytes_fp32(Q.fmt));
     // ---- stage 0: inputs n = o + m0*D - (L-1) + i; n < 0 from the history (one load expression for both sources)
     const int64_t nbase = Q.o + m0 * D - (L - 1);
     for (int i = tid; i < nxs; i += kPfbThreads) {
@@ -174,10 +173,17 @@ __global__ __launch_bounds__(kPfbThreads) void k_pfb(const void *__restrict__ iq
 //   pass 1   thread (mi, n2): SmallDft<M1> over n1 in place in the exchange tile, times the middle twiddle
 //   pass 2   thread (k1, mi): SmallDft<M2> over n2, stores channels k1 + M1*k2; consecutive lanes hold
 //            consecutive output times, so each channel row receives TB*8 contiguous bytes.
+// wire_format.hpp's fp32 decode of a packed sample on the kernel's vector type (both components in one packed operation)
+template <int FMT>
+__device__ __forceinline__ cf32v pfb_decode(uint32_t w)
+{
+    const cf32v c = cv((float)wire_code_i<FMT>(w), (float)wire_code_q<FMT>(w)) * WireScale<FMT>::f32;
+    return WireScale<FMT>::biased ? c - cv(1.f, 1.f) : c;
+}
 template <int FMT>
 struct PfbUnit;   // four consecutive input samples in wire format + validity
 template <>
-struct PfbUnit<2> {
+struct PfbUnit<FMT_CF32> {
     float4 a, b;
     uint32_t ok;
     __device__ __forceinline__ void load(const char *base, const char *hend, int64_t hv, int64_t n0, int64_t n_in)
@@ -211,7 +217,7 @@ struct PfbUnit<2> {
     }
 };
 template <>
-struct PfbUnit<4> {   // cs16: 16 bytes at a 4-byte aligned address; a word is int16 I (low half), int16 Q
+struct PfbUnit<FMT_CS16> {   // cs16: 16 bytes at a 4-byte aligned address; a word is int16 I (low half), int16 Q
     uint4 v;
     uint32_t ok;
     __device__ __forceinline__ void load(const char *base, const char *hend, int64_t hv, int64_t n0, int64_t n_in)
@@ -236,7 +242,7 @@ struct PfbUnit<4> {   // cs16: 16 bytes at a 4-byte aligned address; a word is i
     }
     __device__ __forceinline__ static cf32v conv(uint32_t w)
     {
-        return cv((float)(int16_t)(w & 65535u), (float)((int32_t)w >> 16)) * 0x1p-15f;
+        return pfb_decode<FMT_CS16>(w);
     }
     __device__ __forceinline__ void store(cf32v *dst) const
     {
@@ -250,7 +256,7 @@ struct PfbUnit<4> {   // cs16: 16 bytes at a 4-byte aligned address; a word is i
     }
 };
 template <int FMT>
-struct PfbUnit {   // cu8 (FMT 0) / cs8 (FMT 1): 8 bytes
+struct PfbUnit {   // FMT_CU8 / FMT_CS8: 8 bytes
     uint2 v;
     uint32_t ok;
     __device__ __forceinline__ void load(const char *base, const char *hend, int64_t hv, int64_t n0, int64_t n_in)
@@ -277,8 +283,7 @@ struct PfbUnit {   // cu8 (FMT 0) / cs8 (FMT 1): 8 bytes
     }
     __device__ __forceinline__ static cf32v conv(uint32_t h)   // low 16 bits: I, Q
     {
-        if (FMT == 0) return cv((float)(h & 255u), (float)((h >> 8) & 255u)) * (1.f / 127.5f) - cv(1.f, 1.f);
-        return cv((float)(int8_t)(h & 255u), (float)(int8_t)((h >> 8) & 255u)) * (1.f / 128.f);
+        return pfb_decode<FMT>(h);
     }
     __device__ __forceinline__ void store(cf32v *dst) const
     {
@@ -402,7 +407,7 @@ __global__ __launch_bounds__(TB *M2, pfb_waves_per_simd(TB *M2, WGS)) void k_pfb
     // (in LDS rather than re-read from memory: loads and stores share vmcnt, so a global load issued after
     //  pass 2's stores would wait for their write acknowledgements)
     const char *iq = (const char *)iq_ + (int64_t)blockIdx.y * Q.in_stride;
-    const char *hend = CARRY ? pfb_hist_end<L>(Q, blockIdx.y, pfb_fmt_bytes(FMT)) : nullptr;
+    const char *hend = CARRY ? pfb_hist_end<L>(Q, blockIdx.y, wire_bytes(FMT)) : nullptr;
     const int64_t hv = CARRY ? Q.hist_valid : 0, o = CARRY ? Q.o : 0;
     cf32v *out = out_ + (int64_t)blockIdx.y * Q.out_batch;
     const int tid = threadIdx.x;

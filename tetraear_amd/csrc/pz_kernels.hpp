@@ -82,19 +82,13 @@ struct RawLoaderRT {
     // C carriers shifted out of each of T consecutive chunks of one stream in one call (plan rows = T x C)
     int32_t rows_per_chunk;
 
-    TDM_HD int bytes() const { return (fmt == FMT_CU8 || fmt == FMT_CS8) ? 2 : (fmt == FMT_CS16 ? 4 : (fmt == FMT_CF32 ? 8 : 16)); }
+    TDM_HD int bytes() const { return wire_bytes(fmt); }
     TDM_HD const void *row_ptr(int row) const { return (const char *)iq + (int64_t)(rows_per_chunk > 1 ? row / rows_per_chunk : row) * row_stride * bytes(); }
     TDM_HD double row_shift(int row) const { return (SHIFT && pre_shift) ? pre_shift[row] : 0.0; }
 
     TDM_HD void raw(const void *rowp, int64_t k, double &re, double &im) const
     {
-        switch (fmt) {
-        case FMT_CU8: convert_one<FMT_CU8>(rowp, k, re, im); break;
-        case FMT_CS8: convert_one<FMT_CS8>(rowp, k, re, im); break;
-        case FMT_CF32: convert_one<FMT_CF32>(rowp, k, re, im); break;
-        case FMT_CS16: convert_one<FMT_CS16>(rowp, k, re, im); break;
-        default: convert_one<FMT_CF64>(rowp, k, re, im); break;
-        }
+        wire_dispatch(fmt, [&](auto F) TDM_WIRE_INLINE { convert_one<decltype(F)::value>(rowp, k, re, im); });
     }
     TDM_HD void sample(const void *rowp, int64_t k, double f, double &re, double &im) const
     {
@@ -144,28 +138,15 @@ struct RawLoaderRT {
 #pragma unroll
             for (int i = 0; i < L; ++i) {
                 const uint32_t s = w[i / 2] >> (16 * (i % 2));
-                cvt8<FMT>(s & 255u, (s >> 8) & 255u, xr[i], xi[i]);
+                wire_f64_bytes<FMT>(s & 255u, (s >> 8) & 255u, xr[i], xi[i]);
             }
         } else {
             const uint16_t *h = (const uint16_t *)p;
 #pragma unroll
             for (int i = 0; i < L; ++i) {
                 const uint32_t s = h[i];
-                cvt8<FMT>(s & 255u, (s >> 8) & 255u, xr[i], xi[i]);
+                wire_f64_bytes<FMT>(s & 255u, (s >> 8) & 255u, xr[i], xi[i]);
             }
-        }
-    }
-    template <int FMT>
-    TDM_HD static void cvt8(uint32_t a, uint32_t b, double &re, double &im)
-    {
-        if (FMT == FMT_CU8) {
-            // pyrtlsdr: bytes.astype(float64) / 127.5 - 1 with numpy's multiply by fl(1/127.5): two roundings
-            const double cc = 1.0 / 127.5;
-            re = sub_rn(mul_rn((double)a, cc), 1.0);
-            im = sub_rn(mul_rn((double)b, cc), 1.0);
-        } else {
-            re = (double)(int8_t)a * (1.0 / 128.0);
-            im = (double)(int8_t)b * (1.0 / 128.0);
         }
     }
 
@@ -194,6 +175,8 @@ struct RawLoaderRT {
                     nco.init(k, f, fs);
                 }
             }
+            // (spelled out, not wire_dispatch: the order in which the compiler lays these five bodies out decides
+            // k_pz_block's register allocation -- at 256 VGPRs, its spills -- and through the dispatcher it comes out another)
             switch (fmt) {
             case FMT_CU8: fast8<L, FMT_CU8>(p, xr, xi); break;
             case FMT_CS8: fast8<L, FMT_CS8>(p, xr, xi); break;
@@ -218,10 +201,7 @@ struct RawLoaderRT {
 #pragma unroll
                 for (int i = 4 * NQ; i < L; ++i) w[i] = ((const uint32_t *)p)[i];
 #pragma unroll
-                for (int i = 0; i < L; ++i) {
-                    xr[i] = (double)(int16_t)(w[i] & 65535u) * 0x1p-15;
-                    xi[i] = (double)((int32_t)w[i] >> 16) * 0x1p-15;
-                }
+                for (int i = 0; i < L; ++i) wire_f64<FMT_CS16>(w[i], xr[i], xi[i]);
             } break;
             default: {
                 const f64x2_a8 *v = (const f64x2_a8 *)p;

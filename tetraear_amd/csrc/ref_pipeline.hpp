@@ -173,13 +173,10 @@ template <class BE>
 void run_ref(BE &be, const RefPlanHost &h, int rows, int fmt, const RefBuffers &B, const RefIO &io)
 {
     const bool sh = io.pre_shift != nullptr;
-    switch (fmt) {
-    case FMT_CU8: sh ? run_ref_fmt<BE, FMT_CU8, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CU8, false>(be, h, rows, B, io); break;
-    case FMT_CS8: sh ? run_ref_fmt<BE, FMT_CS8, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CS8, false>(be, h, rows, B, io); break;
-    case FMT_CF32: sh ? run_ref_fmt<BE, FMT_CF32, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CF32, false>(be, h, rows, B, io); break;
-    case FMT_CS16: sh ? run_ref_fmt<BE, FMT_CS16, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CS16, false>(be, h, rows, B, io); break;
-    default: sh ? run_ref_fmt<BE, FMT_CF64, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT_CF64, false>(be, h, rows, B, io); break;
-    }
+    wire_dispatch<kWireRefPlan>(fmt, [&](auto F) {
+        constexpr int FMT = decltype(F)::value;
+        sh ? run_ref_fmt<BE, FMT, true>(be, h, rows, B, io) : run_ref_fmt<BE, FMT, false>(be, h, rows, B, io);
+    });
 }
 
 // convert body: raw sample (+ input-rate pre-shift) then process()'s freq_offset at rate fs

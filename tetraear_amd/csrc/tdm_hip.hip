@@ -649,8 +649,8 @@ static int plan_select(tdm_plan *plan, double sample_rate, int64_t n)
     return TDM_OK;
 }
 
-static size_t fmt_bytes(int fmt) { return fmt == TDM_CU8 || fmt == TDM_CS8 ? 2 : (fmt == TDM_CS16 ? 4 : (fmt == TDM_CF32 ? 8 : 16)); }
-static int tetra_fmt8(int fmt) { return fmt == TDM_CU8 ? 1 : (fmt == TDM_CS8 ? 2 : (fmt == TDM_CS16 ? 3 : 0)); }   // the TETRA-mode kernels' FMT8
+static_assert(FMT_CU8 == TDM_CU8 && FMT_CS8 == TDM_CS8 && FMT_CF32 == TDM_CF32 && FMT_CF64 == TDM_CF64 && FMT_CS16 == TDM_CS16,
+              "wire_format.hpp numbers the formats as include/tetrahip.h does");
 
 // Geometry of a chunk walked in K pieces (oracle/tetra_np.py gardner_segments is the same arithmetic): false when the chunk is
 // too short (a piece's own part, n / K, under 1.9 warm-ups)
@@ -795,7 +795,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
     if (!out) return fail(TDM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!(sample_rate > 0) || n_samples < 1 || n_samples > (int64_t(1) << 31) || n_carriers < 1 || n_carriers > 65535 ||
-        in_fmt < 0 || in_fmt > TDM_CS16)
+        !wire_accepts(kWireRefPlan, in_fmt))
         return fail(TDM_ERR_INVALID, "bad sample_rate / n_samples / n_carriers (1..65535) / in_fmt");
     if (mode != TDM_MODE_REFERENCE && mode != TDM_MODE_TETRA && mode != TDM_MODE_TETRA_GARDNER) return fail(TDM_ERR_INVALID, "bad mode");
     int rc = use_device(device);
@@ -810,7 +810,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
         // channelised baseband as cf32 (the channeliser's output), or straight off the wire as cu8 / cs8 (round 6: converted where
         // the kernels stage their window; one bf16 plane per component in the fused receiver)
         // (cs16: packed like the bytes, but staged as the cf32 values it means -- the cf32 arithmetic behind the loader)
-        if (in_fmt == TDM_CF64) return fail(TDM_ERR_UNSUPPORTED, "TETRA mode takes cf32, cu8, cs8 or cs16 baseband");
+        if (!wire_accepts(kWireTetra, in_fmt)) return fail(TDM_ERR_UNSUPPORTED, "TETRA mode takes cf32, cu8, cs8 or cs16 baseband");
         const double sps = sample_rate / kSymbolRate;
         if (sps < 2.0 || sps > 8.0) return fail(TDM_ERR_UNSUPPORTED, "TETRA mode needs 2..8 samples per symbol");
         if (n_samples < 64 || n_samples > (int64_t)kMaxTimingBlocks * kTimingBlock)
@@ -874,7 +874,7 @@ int tdm_plan_create(double sample_rate, int64_t n_samples, int32_t n_carriers, i
             p->device = device;
             // (8-bit input: the fused kernel is instantiated for 33 and 35 taps; other tap counts, and cs16 at every tap count,
             //  take the three launches, whose matched filter converts)
-            p->gardner_fused_ok = (debug_value("gardner_fused") != 0 && tetra_gardner_fused_available(tp.ntaps, n_carriers, tetra_fmt8(in_fmt))) ? 1 : 0;
+            p->gardner_fused_ok = (debug_value("gardner_fused") != 0 && tetra_gardner_fused_available(tp.ntaps, n_carriers, in_fmt)) ? 1 : 0;
             p->gardner_ntaps_design = ntaps_design;
             {
                 // (no memory for the pieces' temporaries: the plan is made all the same and walks whole chunks)
@@ -1044,7 +1044,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
                 S.ff_first = plan->gardner_ff_first;
                 {
                     HipBackend::Scope s(be, ST_TETRA_LOOP);
-                    fused_done = tetra_gardner_fused_launch(plan->gtp, K * R, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, plan->d_gsoft.get(),
+                    fused_done = tetra_gardner_fused_launch(plan->gtp, K * R, iq, plan->fmt, carrier_stride_samples, plan->d_gsoft.get(),
                                                             plan->d_gint.get(), plan->d_gint.get() + (size_t)K * R, be.stream, &S);
                 }
                 if (fused_done) {
@@ -1064,7 +1064,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
                 HipBackend::Scope s(be, ST_TETRA_LOOP);
                 GardnerSeg S{};
                 S.ff_first = plan->gardner_ff_first;
-                fused_done = tetra_gardner_fused_launch(tp, plan->rows, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, (float2 *)soft, n_soft, best_phase, be.stream,
+                fused_done = tetra_gardner_fused_launch(tp, plan->rows, iq, plan->fmt, carrier_stride_samples, (float2 *)soft, n_soft, best_phase, be.stream,
                                                         S.ff_first ? &S : nullptr);
             }
             if (plan->gardner_ff_first && !fused_done)
@@ -1074,7 +1074,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
                 HIP_TRY(dev_alloc(plan->d_gy, (size_t)plan->rows * plan->gy_pitch * sizeof(float2)));
             if (three && (stages & 1)) {
                 HipBackend::Scope s(be, ST_TETRA_MF);
-                if (!tetra_mf_launch(tp, plan->rows, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, plan->d_gy.get(), plan->gy_pitch, be.stream))
+                if (!tetra_mf_launch(tp, plan->rows, iq, plan->fmt, carrier_stride_samples, plan->d_gy.get(), plan->gy_pitch, be.stream))
                     return fail(TDM_ERR_UNSUPPORTED, "no RRC kernel instantiated for this tap count");
             }
             if (three && (stages & 2)) {
@@ -1091,7 +1091,7 @@ static int process_device_impl(tdm_plan *plan, const void *iq, int64_t carrier_s
         {
             // one kernel: matched filter, timing, Farrow, carrier-offset estimate and decisions; one workgroup per carrier
             HipBackend::Scope s(be, ST_TETRA);
-            if (!tetra_launch(tp, plan->rows, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, (float2 *)soft, hard, n_soft, best_phase,
+            if (!tetra_launch(tp, plan->rows, iq, plan->fmt, carrier_stride_samples, (float2 *)soft, hard, n_soft, best_phase,
                               min_margin, be.stream, row_list, n_rows))
                 return fail(TDM_ERR_UNSUPPORTED, "no RRC kernel instantiated for this tap count");
         }
@@ -1143,7 +1143,7 @@ int tdm_plan_rrc_filter(tdm_plan *plan, const void *iq, int64_t carrier_stride_s
     be.timer = &plan->timer;
     {
         HipBackend::Scope s(be, ST_TETRA_MF);
-        if (!tetra_mf_launch(plan->tp, plan->rows, iq, tetra_fmt8(plan->fmt), carrier_stride_samples, (float2 *)y, y_pitch, be.stream))
+        if (!tetra_mf_launch(plan->tp, plan->rows, iq, plan->fmt, carrier_stride_samples, (float2 *)y, y_pitch, be.stream))
             return fail(TDM_ERR_UNSUPPORTED, "no RRC kernel instantiated for this tap count");
     }
     if (be.err != hipSuccess) return fail(TDM_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(be.err));
@@ -1197,7 +1197,7 @@ int tdm_process(tdm_plan *plan, const void *iq, int64_t carrier_stride_samples, 
     const int in_rows = plan->mode == TDM_MODE_REFERENCE ? rows / plan->rows_per_chunk : rows;
     const size_t span = carrier_stride_samples == 0 ? (size_t)h.n
                                                     : (size_t)(in_rows - 1) * carrier_stride_samples + h.n;
-    const size_t bytes = span * fmt_bytes(plan->fmt);
+    const size_t bytes = span * wire_bytes(plan->fmt);
     if (plan->d_iq_bytes < bytes) {
         plan->d_iq_bytes = 0;
         HIP_TRY(dev_alloc(plan->d_iq, bytes));
@@ -1248,7 +1248,7 @@ int tdm_process_pipelined(tdm_plan *plan, const void *iq, int64_t n_batches, con
     //  pre-shifts, which this entry point does not take: such a plan goes through tdm_process)
     if (plan->mode == TDM_MODE_REFERENCE && plan->rows_per_chunk > 1)
         return fail(TDM_ERR_UNSUPPORTED, "tdm_process_pipelined: the plan has rows_per_chunk > 1 (use tdm_process / tdm_process_device)");
-    const size_t in_bytes = (size_t)rows * h.n * fmt_bytes(plan->fmt);
+    const size_t in_bytes = (size_t)rows * h.n * wire_bytes(plan->fmt);
     const size_t soft_elem = plan->mode != TDM_MODE_REFERENCE ? 2 * sizeof(float) : 2 * sizeof(double);
     const size_t hard_bytes = (size_t)rows * h.max_soft, soft_bytes = (size_t)rows * h.max_soft * soft_elem;
     // pin the caller's buffers in place so the copies are truly asynchronous (best effort; host_pin leaves a buffer that is
@@ -1369,7 +1369,7 @@ int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int
     if (!(sample_rate > 0) || n_samples < 1 || n_samples > (int64_t(1) << 31) || n_rows < 1 || n_rows > 65535)
         return fail(TDM_ERR_INVALID, "tdm_stream_create: bad sample_rate / n_samples / n_rows (1..65535)");
     // (cs16 is not taken here yet: the host-fed stream's slots are sized and checked for the four formats below)
-    if (in_fmt < 0 || in_fmt > TDM_CF64) return fail(TDM_ERR_INVALID, "tdm_stream_create: bad in_fmt (cu8, cs8, cf32 or cf64)");
+    if (!wire_accepts(kWireStream, in_fmt)) return fail(TDM_ERR_INVALID, "tdm_stream_create: bad in_fmt (cu8, cs8, cf32 or cf64)");
     if (mode != TDM_MODE_REFERENCE && mode != TDM_MODE_TETRA && mode != TDM_MODE_TETRA_GARDNER)
         return fail(TDM_ERR_INVALID, "tdm_stream_create: bad mode");
     if (flags & ~TDM_STREAM_SOFT) return fail(TDM_ERR_INVALID, "tdm_stream_create: unknown flags");
@@ -1399,7 +1399,7 @@ int tdm_stream_create(double sample_rate, int64_t n_samples, int32_t n_rows, int
         x.st = plan->stream.get();
     }
     s->max_soft = (int32_t)s->slots[0].plan->h().max_soft;
-    const size_t in_bytes = (size_t)s->in_rows * n_samples * fmt_bytes(in_fmt);
+    const size_t in_bytes = (size_t)s->in_rows * n_samples * wire_bytes(in_fmt);
     const size_t hard_bytes = (size_t)n_rows * s->max_soft, soft_bytes = hard_bytes * s->soft_elem;
     const unsigned in_flags = debug_value("stream_wc") == 1 ? hipHostMallocWriteCombined : hipHostMallocDefault;
     for (auto &x : s->slots) {
@@ -1460,7 +1460,7 @@ int tdm_stream_acquire(tdm_stream *s, void **iq, int64_t *seq)
 // the enqueue of one step on slot x (tdm_stream_submit; it drains the slot when this fails part of the way)
 static int stream_enqueue(tdm_stream *s, StreamSlot &x, int64_t n_samples, int32_t n_valid_inputs, int32_t valid_rows, int32_t ms)
 {
-    const size_t bytes = (size_t)n_valid_inputs * n_samples * fmt_bytes(s->fmt), hard_bytes = (size_t)s->rows * ms;
+    const size_t bytes = (size_t)n_valid_inputs * n_samples * wire_bytes(s->fmt), hard_bytes = (size_t)s->rows * ms;
     HIP_TRY(hipStreamWaitEvent(s->s_h2d.get(), x.ev_done.get(), 0));   // the slot's previous step no longer reads its device input
     HIP_TRY(hipMemcpyAsync(x.d_iq.get(), x.h_iq.get(), bytes, hipMemcpyHostToDevice, s->s_h2d.get()));
     HIP_TRY(hipEventRecord(x.ev_in.get(), s->s_h2d.get()));
@@ -2231,7 +2231,7 @@ int tdm_resample(const double *x, int64_t n, int64_t num, double *y, int32_t dev
 int tdm_spectrum_gate(const void *iq, int32_t in_fmt, int64_t row_stride, int64_t n_samples, int32_t rows,
                       double sample_rate, double *out, double *afc, int32_t device_pointers, int32_t device)
 {
-    if (!iq || !out || rows < 1 || n_samples < 0 || in_fmt < 0 || in_fmt > TDM_CS16 || !(sample_rate > 0))
+    if (!iq || !out || rows < 1 || n_samples < 0 || !wire_accepts(kWireGate, in_fmt) || !(sample_rate > 0))
         return fail(TDM_ERR_INVALID, "bad argument");
     int rc = use_device(device);
     if (rc) return rc;
@@ -2247,7 +2247,7 @@ int tdm_spectrum_gate(const void *iq, int32_t in_fmt, int64_t row_stride, int64_
     const int64_t used = n_samples < kGateFft ? n_samples : kGateFft;  // only the first 2048 samples of a row matter
     if (!device_pointers) {
         // upload just the leading samples of every row
-        const size_t eb = fmt_bytes(in_fmt);
+        const size_t eb = wire_bytes(in_fmt);
         if ((rc = din.alloc((size_t)rows * (used ? used : 1) * eb)) || (rc = dout.alloc((size_t)rows * kGateOut * 8)) ||
             (rc = dafc.alloc((size_t)rows * 8)))
             return rc;
@@ -2516,7 +2516,7 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
     Q.W1 = tb.tw;
     Q.WM = Q.W1 + M1 * M1;
     Q.W2 = Q.WM + M;
-    Q.in_stride = n_in * (int64_t)fmt_bytes(fmt);
+    Q.in_stride = n_in * (int64_t)wire_bytes(fmt);
     Q.out_batch = (int64_t)M * pitch;
     const bool force_direct = debug_value("pfb_direct") == 1;
     if (!force_direct && D <= 4 * M) {
@@ -2550,21 +2550,11 @@ int launch_pfb(int device, const void *iq, int fmt, int64_t n_in, int D, float2 
             const unsigned threads = TB * M2;
             {
                 const bool one = nu <= TB * M2;   // one prefetched unit per thread covers the window
-                if (carry) {
-                    switch (fmt) {
-                    case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS, true>; break;
-                    case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS, true>; break;
-                    case TDM_CS16: kern = one ? k_pfb_fft<M1, M2, P, TB, 4, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 4, 2, WGS, true>; break;
-                    default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS, true>; break;
-                    }
-                } else {
-                    switch (fmt) {
-                    case TDM_CU8: kern = one ? k_pfb_fft<M1, M2, P, TB, 0, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 0, 2, WGS, false>; break;
-                    case TDM_CS8: kern = one ? k_pfb_fft<M1, M2, P, TB, 1, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 1, 2, WGS, false>; break;
-                    case TDM_CS16: kern = one ? k_pfb_fft<M1, M2, P, TB, 4, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 4, 2, WGS, false>; break;
-                    default: kern = one ? k_pfb_fft<M1, M2, P, TB, 2, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, 2, 2, WGS, false>; break;
-                    }
-                }
+                kern = wire_dispatch<kWireChan, FMT_CF32>(fmt, [&](auto F) {
+                    constexpr int FMT = decltype(F)::value;
+                    return carry ? (one ? k_pfb_fft<M1, M2, P, TB, FMT, 1, WGS, true> : k_pfb_fft<M1, M2, P, TB, FMT, 2, WGS, true>)
+                                 : (one ? k_pfb_fft<M1, M2, P, TB, FMT, 1, WGS, false> : k_pfb_fft<M1, M2, P, TB, FMT, 2, WGS, false>);
+                });
             }
             HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             const unsigned blocks = (unsigned)((rounds + Q.G - 1) / Q.G);
@@ -2644,7 +2634,7 @@ int tdm_channelise_batch(const void *iq, int32_t in_fmt, int64_t n_in, int32_t n
 {
     if (!iq || !out || !n_out || n_in < 1 || D < 1 || n_streams < 1 || n_streams > 65535 ||
         (out_pitch != 0 && out_pitch < (n_in + D - 1) / D) ||
-        (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32 && in_fmt != TDM_CS16))
+        !wire_accepts(kWireChan, in_fmt))
         return fail(TDM_ERR_INVALID, "bad argument");
     int rc = use_device(device);
     if (rc) return rc;
@@ -2654,7 +2644,7 @@ int tdm_channelise_batch(const void *iq, int32_t in_fmt, int64_t n_in, int32_t n
     DevBuf din, dout;
     const void *src = iq;
     float2 *dst = (float2 *)out;
-    const size_t ib = (size_t)n_streams * n_in * fmt_bytes(in_fmt), ob = (size_t)n_streams * M * pitch * sizeof(float2);
+    const size_t ib = (size_t)n_streams * n_in * wire_bytes(in_fmt), ob = (size_t)n_streams * M * pitch * sizeof(float2);
     if (!device_pointers) {
         if ((rc = din.alloc(ib)) || (rc = dout.alloc(ob))) return rc;
         HIP_TRY(hipMemcpy(din.p, iq, ib, hipMemcpyHostToDevice));
@@ -2767,7 +2757,7 @@ int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_strea
     // every refusal before the first HIP call
     if (!out) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: out is null");
     *out = nullptr;
-    if (in_fmt != TDM_CU8 && in_fmt != TDM_CS8 && in_fmt != TDM_CF32 && in_fmt != TDM_CS16)
+    if (!wire_accepts(kWireChan, in_fmt))
         return fail(TDM_ERR_INVALID, "tdm_channeliser_create: in_fmt must be cu8, cs8, cs16 or cf32");
     if (D < 1) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: decimation D < 1");
     if (n_streams < 1 || n_streams > 65535) return fail(TDM_ERR_INVALID, "tdm_channeliser_create: n_streams 1..65535");
@@ -2787,7 +2777,7 @@ int tdm_channeliser_create(int32_t M, int32_t D, int32_t in_fmt, int32_t n_strea
     PfbTablesOp tabs{device, D, 0};
     if ((rc = pfb_for_m(M, tabs))) return rc;   // (made here: a push allocates nothing)
     ch->L = tabs.L;
-    const int fb = pfb_fmt_bytes(in_fmt);
+    const int fb = wire_bytes(in_fmt);
     ch->hist_stride = (int64_t)(ch->L - 1) * fb;
     ch->pitch_dev = (max_n_in + D - 1) / D;
     ch->pitch_dev = (ch->pitch_dev + 15) / 16 * 16;
@@ -2819,7 +2809,7 @@ int tdm_channeliser_push(tdm_channeliser *ch, const void *iq, int64_t n_in, floa
         return fail(TDM_ERR_INVALID, "tdm_channeliser_push: out_pitch must hold ceil(n_in / D) (or be 0: this push's n_out)");
     const ChanPush p = chan_push(ch->samples_in, n_in, M, D, ch->L);
     const int64_t pitch = out_pitch ? out_pitch : p.n_out;
-    const int fb = pfb_fmt_bytes(ch->fmt);
+    const int fb = wire_bytes(ch->fmt);
     HIP_TRY(hipSetDevice(ch->device));
     hipStream_t st = device_pointers ? g_cur_stream : ch->st.get();
     HIP_TRY(hipStreamWaitEvent(st, ch->ev_last.get(), 0));   // behind the previous push, on whatever stream it ran

@@ -7,17 +7,14 @@
 namespace tdm {
 
 
-bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *soft, uint8_t *hard,
+bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt, int64_t in_stride, float2 *soft, uint8_t *hard,
                   int32_t *n_soft, int32_t *timing_milli, double *min_margin, hipStream_t stream, const int32_t *row_list,
                   const int32_t *n_rows)
 {
     switch (tp.ntaps) {
 #define TDM_RRC_ARGS dim3(rows), dim3(kRrcThreads), 0, stream, x, in_stride, tp, soft, hard, n_soft, timing_milli, min_margin, row_list, n_rows
-#define TDM_RRC_CASE(NT) case NT:                                                      \
-        if (fmt8 == 1) hipLaunchKernelGGL((k_tetra_fused<NT, 1>), TDM_RRC_ARGS);         \
-        else if (fmt8 == 2) hipLaunchKernelGGL((k_tetra_fused<NT, 2>), TDM_RRC_ARGS);    \
-        else if (fmt8 == 3) hipLaunchKernelGGL((k_tetra_fused<NT, 3>), TDM_RRC_ARGS);    \
-        else hipLaunchKernelGGL((k_tetra_fused<NT, 0>), TDM_RRC_ARGS);                   \
+#define TDM_RRC_CASE(NT) case NT:                                                                                                  \
+        wire_dispatch<kWireTetra, FMT_CF32>(fmt, [&](auto F) { hipLaunchKernelGGL((k_tetra_fused<NT, decltype(F)::value>), TDM_RRC_ARGS); }); \
         return true;
         TDM_RRC_CASE(17) TDM_RRC_CASE(25) TDM_RRC_CASE(33) TDM_RRC_CASE(35) TDM_RRC_CASE(41) TDM_RRC_CASE(49) TDM_RRC_CASE(57) TDM_RRC_CASE(65)
 #undef TDM_RRC_CASE
@@ -26,16 +23,15 @@ bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int6
     }
 }
 
-bool tetra_mf_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *y, int64_t y_pitch, hipStream_t stream)
+bool tetra_mf_launch(const TetraParams &tp, int rows, const void *x, int fmt, int64_t in_stride, float2 *y, int64_t y_pitch, hipStream_t stream)
 {
     const int tiles = (tp.n + kMfTile - 1) / kMfTile;
     const dim3 grid((unsigned)((tiles + kMfTilesPerWg - 1) / kMfTilesPerWg), (unsigned)rows);
     switch (tp.ntaps) {
-#define TDM_MF_CASE(NT) case NT:                                                                                                             \
-        if (fmt8 == 1) hipLaunchKernelGGL((k_tetra_mf<NT, 1>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);              \
-        else if (fmt8 == 2) hipLaunchKernelGGL((k_tetra_mf<NT, 2>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);         \
-        else if (fmt8 == 3) hipLaunchKernelGGL((k_tetra_mf<NT, 3>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);         \
-        else hipLaunchKernelGGL((k_tetra_mf<NT, 0>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch);                        \
+#define TDM_MF_CASE(NT) case NT:                                                                                                       \
+        wire_dispatch<kWireTetra, FMT_CF32>(fmt, [&](auto F) {                                                                         \
+            hipLaunchKernelGGL((k_tetra_mf<NT, decltype(F)::value>), grid, dim3(kMfThreads), 0, stream, x, in_stride, tp, y, y_pitch); \
+        });                                                                                                                            \
         return true;
         TDM_MF_CASE(17) TDM_MF_CASE(25) TDM_MF_CASE(33) TDM_MF_CASE(35) TDM_MF_CASE(41) TDM_MF_CASE(49) TDM_MF_CASE(57) TDM_MF_CASE(65)
 #undef TDM_MF_CASE
@@ -76,12 +72,12 @@ static const void *gardner_fused_kernel(int ntaps)
 // With two per unit it stays ahead of the three launches at any size (4096 / 8192 / 16 384 carriers at 4 samples per
 // symbol: 1.35 / 1.86 / 3.51 ms against 1.85 / 2.4 / 3.57); with one per unit only while the launch is a single round (the
 // loop on its own needs 33 KB and runs four workgroups per unit: 8192 carriers at 8 samples per symbol 1.96 ms).
-bool tetra_gardner_fused_available(int ntaps, int rows, int fmt8)
+bool tetra_gardner_fused_available(int ntaps, int rows, int fmt)
 {
     const void *fn = gardner_fused_kernel(ntaps);
     if (!fn) return false;
-    if (fmt8 == 3) return false;                            // (cs16: no fused instantiation, the three launches)
-    if (fmt8 && ntaps != 33 && ntaps != 35) return false;   // (tetra_gardner_fused_launch: the 8-bit instantiations)
+    if (fmt == FMT_CS16) return false;                                   // (cs16: no fused instantiation, the three launches)
+    if (wire_packed8(fmt) && ntaps != 33 && ntaps != 35) return false;   // (tetra_gardner_fused_launch: the 8-bit instantiations)
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return true;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kGWaves, 0) != hipSuccess || per_cu < 1) return true;
@@ -96,19 +92,20 @@ int tetra_gardner_fused_per_cu(int ntaps)
     return per_cu;
 }
 
-bool tetra_gardner_fused_launch(const TetraParams &tp, int rows, const void *x_, int fmt8, int64_t in_stride, float2 *soft, int32_t *n_soft,
+bool tetra_gardner_fused_launch(const TetraParams &tp, int rows, const void *x_, int fmt, int64_t in_stride, float2 *soft, int32_t *n_soft,
                                 int32_t *timing_milli, hipStream_t stream, const GardnerSeg *seg)
 {
     const GardnerSeg S = seg ? *seg : GardnerSeg{};
     const GardnerConsts G = gardner_gains();
     const dim3 grid((unsigned)((rows + kGQuads - 1) / kGQuads)), block(64 * kGWaves);
     const float2 *x = (const float2 *)x_;
-    if (fmt8 == 3) return false;   // (cs16 takes the three launches: tetra_gardner_fused_available)
-    if (fmt8) {   // 8-bit input: the tap counts of 4 and 4.44 samples per symbol (72 / 80 kS/s) -- the others take the three launches
+    if (fmt == FMT_CS16) return false;   // (cs16 takes the three launches: tetra_gardner_fused_available)
+    if (wire_packed8(fmt)) {   // 8-bit input: the tap counts of 4 and 4.44 samples per symbol (72 / 80 kS/s) -- the others take the three launches
         switch (tp.ntaps) {
-#define TDM_GF8_CASE(NT) case NT:                                                                                                                  \
-            if (fmt8 == 1) hipLaunchKernelGGL((k_tetra_gardner<NT, 1>), grid, block, 0, stream, x, in_stride, tp, G, rows, soft, n_soft, timing_milli, S); \
-            else hipLaunchKernelGGL((k_tetra_gardner<NT, 2>), grid, block, 0, stream, x, in_stride, tp, G, rows, soft, n_soft, timing_milli, S);           \
+#define TDM_GF8_CASE(NT) case NT:                                                                                                                            \
+            wire_dispatch<wire_bit(FMT_CU8) | wire_bit(FMT_CS8), FMT_CS8>(fmt, [&](auto F) {                                                                 \
+                hipLaunchKernelGGL((k_tetra_gardner<NT, decltype(F)::value>), grid, block, 0, stream, x, in_stride, tp, G, rows, soft, n_soft, timing_milli, S); \
+            });                                                                                                                                              \
             return true;
             TDM_GF8_CASE(33) TDM_GF8_CASE(35)
 #undef TDM_GF8_CASE

@@ -64,22 +64,16 @@ constexpr int kMfThreads = 256, kMfPer = 8, kMfTile = kMfThreads * kMfPer, kMfTi
 //   * ONE tile per workgroup: 0.371 ms = 5.79 TB/s = 0.72 of 8 TB/s.  (A workgroup walking 2 / 4 / 8 tiles with the next
 //     window in flight: 0.377 / 0.390 / 0.424 ms -- with seven workgroups per compute unit the dispatcher's interleaving
 //     hides the load phase better than a static walk does.)
-// FMT8: 0 = cf32 input (above); 1 = cu8, 2 = cs8 (north_star: "coalesced complex-int8/float loads"): the window arrives as
+// FMT: FMT_CF32 input (above); FMT_CU8, FMT_CS8 (north_star: "coalesced complex-int8/float loads"): the window arrives as
 // 2-byte samples -- 10 instead of 16 bytes per sample through HBM -- and is converted where it is staged,
-// cu8 as pyrtlsdr and the channeliser do (u * fl(1/127.5) - 1 in fp32), cs8 as s / 128; everything behind the staging is the
-// cf32 kernel.  (2-byte loads, one per sample and thread: a row of bytes has no alignment to speak of, and at 2 of the
+// cu8 as pyrtlsdr and the channeliser do, cs8 as s / 128 (tetra_decode: wire_format.hpp's fp32 decode); everything behind
+// the staging is the cf32 kernel.  (2-byte loads, one per sample and thread: a row of bytes has no alignment to speak of, and at 2 of the
 // kernel's 10 bytes per sample the load instructions are not what bounds it.)
-template <int FMT8>
-__device__ __forceinline__ float2 mf_convert8(uint32_t h)   // low 16 bits: I, Q
-{
-    if (FMT8 == 1) return make_float2((float)(h & 255u) * (1.f / 127.5f) - 1.f, (float)((h >> 8) & 255u) * (1.f / 127.5f) - 1.f);
-    return make_float2((float)(int8_t)(h & 255u) * (1.f / 128.f), (float)(int8_t)((h >> 8) & 255u) * (1.f / 128.f));
-}
-
-// FMT8 == 3: cs16 (one 4-byte word per sample, s * 2^-15): pairs of samples as 8-byte loads where the whole window lies inside the
+//
+// FMT_CS16 (one 4-byte word per sample, s * 2^-15): pairs of samples as 8-byte loads where the whole window lies inside the
 // chunk and the pair address is 8-byte aligned, else one 4-byte load per sample from clamped positions; staged as the floats the cf32
 // call stages, so the output is that call's bit for bit.
-template <int NT, int FMT8 = 0>
+template <int NT, int FMT = FMT_CF32>
 __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict__ x_, int64_t in_stride, const TetraParams P,
                                                          float2 *__restrict__ y, int64_t y_pitch)
 {
@@ -92,9 +86,9 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
     auto slot = [](int s) { return s + 2 * (s >> 3); };
     const int row = blockIdx.y, tid = threadIdx.x, n = P.n;
     const float2 *xr = x + (int64_t)row * in_stride;
-    const uint16_t *xr8 = (const uint16_t *)x_ + (int64_t)row * in_stride;   // (FMT8: one 2-byte sample per element)
+    const uint16_t *xr8 = (const uint16_t *)x_ + (int64_t)row * in_stride;   // (8-bit formats: one 2-byte sample per element)
     const uint32_t *xr16 = (const uint32_t *)x_ + (int64_t)row * in_stride;  // (cs16: one 4-byte sample per element)
-    constexpr bool K8 = FMT8 == 1 || FMT8 == 2, K16 = FMT8 == 3;
+    constexpr bool K8 = wire_packed8(FMT), K16 = FMT == FMT_CS16;
     float2 *yr = y + (int64_t)row * y_pitch;
     // a workgroup walks kMfTilesPerWg consecutive tiles with the NEXT tile's window already on its way from HBM while it
     // works on the current one: the memory pipes never wait for a workgroup's arithmetic phase
@@ -106,7 +100,7 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
     typedef f32x4 __attribute__((aligned(8))) f32x4_a8;   // (rows are 8-byte aligned: pitched channeliser rows)
     f32x4 vp[NLP];
     auto interior = [&](int base) { return base - H >= 0 && base - H + W <= n; };
-    uint32_t v8[NLD];   // (FMT8) the thread's samples of the window as they arrive
+    uint32_t v8[NLD];   // (8-bit formats) the thread's samples of the window as they arrive
     typedef uint32_t u32pair __attribute__((ext_vector_type(2)));
     u32pair v16[NLP];   // (cs16) pairs of the window, or its single samples two to a register pair
     auto pairs16 = [&](int base) { return interior(base) && (((uintptr_t)(xr16 + (base - H))) & 7) == 0; };
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
                 for (int k = 0; k < NLP; ++k) {
                     const int pi = tid + k * kMfThreads;
                     if (k < NLP - 1 || pi < W / 2) {
-                        const float2 a = tetra_conv16(v16[k].x), b = tetra_conv16(v16[k].y);
+                        const float2 a = tetra_decode<FMT_CS16>(v16[k].x), b = tetra_decode<FMT_CS16>(v16[k].y);
                         *(f32x4 *)(xs + slot(2 * pi)) = f32x4{a.x, a.y, b.x, b.y};
                     }
                 }
@@ -171,16 +165,16 @@ __global__ __launch_bounds__(kMfThreads) void k_tetra_mf(const void *__restrict_
                 for (int k = 0; k < NLD; ++k) {
                     const int i = tid + k * kMfThreads, g = base - H + i;
                     const uint32_t q = (k & 1) ? v16[k >> 1].y : v16[k >> 1].x;
-                    if (i < W) xs[slot(i)] = (g >= 0 && g < n) ? tetra_conv16(q) : make_float2(0.f, 0.f);
+                    if (i < W) xs[slot(i)] = (g >= 0 && g < n) ? tetra_decode<FMT_CS16>(q) : make_float2(0.f, 0.f);
                 }
             }
             return;
         }
-        if (K8) {
+        if constexpr (K8) {
 #pragma unroll
             for (int k = 0; k < NLD; ++k) {
                 const int i = tid + k * kMfThreads, g = base - H + i;
-                if (i < W) xs[slot(i)] = (g >= 0 && g < n) ? mf_convert8<FMT8>(v8[k]) : make_float2(0.f, 0.f);
+                if (i < W) xs[slot(i)] = (g >= 0 && g < n) ? tetra_decode<FMT>(v8[k]) : make_float2(0.f, 0.f);
             }
             return;
         }
@@ -313,22 +307,22 @@ constexpr int kQuadOtherPair = 0x4E;         // [2, 3, 0, 1]
 // the producers' ~350 instructions per chunk (33 taps) fit there many times over.  Hand-over at the loop's block boundaries through
 // ONE workgroup barrier per block (no polling): the producers publish how many chunks are complete, the loop how far it has
 // moved on; every wavefront passes the same barriers and leaves after the one at which `done` was set.
-// FMT8 (fused form only; round 6): 0 = cf32 input, 1 = cu8, 2 = cs8 -- the producers fetch 2-byte samples and convert them where
-// they write their window (mf_convert8); everything behind the window is the cf32 kernel.
-template <int NT, int FMT8 = 0>
+// FMT (fused form only; round 6): FMT_CF32 input, FMT_CU8, FMT_CS8 -- the producers fetch 2-byte samples and convert them where
+// they write their window (tetra_decode); everything behind the window is the cf32 kernel.
+template <int NT, int FMT = FMT_CF32>
 __global__ __launch_bounds__(NT > 0 ? 64 * kGWaves : 64) void k_tetra_gardner(const float2 *__restrict__ y, int64_t y_pitch, const TetraParams P,
                                                       const GardnerConsts G, int rows, float2 *__restrict__ soft,
                                                       int32_t *__restrict__ n_soft, int32_t *__restrict__ timing_milli, const GardnerSeg S)
 {
     constexpr bool FUSED = NT > 0;
-    static_assert(FUSED || FMT8 == 0, "the loop alone reads the matched filter's cf32 output");
+    static_assert(FUSED || FMT == FMT_CF32, "the loop alone reads the matched filter's cf32 output");
     // input row of (virtual) carrier v: second halves start seg_off samples into their carrier's row
     auto row_in = [&](int v) {
         v = min(v, rows - 1);
         const int h = S.pieces > 0 ? v / S.rows_phys : 0;     // the piece
         return y + (int64_t)(v - h * S.rows_phys) * y_pitch + (int64_t)h * S.seg_step;
     };
-    auto row_in8 = [&](int v) {                               // (FMT8: the same row as 2-byte samples)
+    auto row_in8 = [&](int v) {                               // (8-bit formats: the same row as 2-byte samples)
         v = min(v, rows - 1);
         const int h = S.pieces > 0 ? v / S.rows_phys : 0;
         return (const uint16_t *)y + (int64_t)(v - h * S.rows_phys) * y_pitch + (int64_t)h * S.seg_step;
@@ -364,7 +358,7 @@ __global__ __launch_bounds__(NT > 0 ? 64 * kGWaves : 64) void k_tetra_gardner(co
             const int n = P.n, j = lane >> 3, gI = lane & 7, car0 = 8 * (wave - 1);
             float2 *xw = xwin + (wave - 1) * 8 * GW::pitch;
             const float2 *xrow[GW::loads];              // this lane's pair of every load, in chunk 0's window
-            const uint16_t *xrow8[GW::loads];           // (FMT8) the carrier's sample 0
+            const uint16_t *xrow8[GW::loads];           // (8-bit formats) the carrier's sample 0
             int xcar[GW::loads], xpr[GW::loads];
 #pragma unroll
             for (int k = 0; k < GW::loads; ++k) {
@@ -378,10 +372,10 @@ __global__ __launch_bounds__(NT > 0 ? 64 * kGWaves : 64) void k_tetra_gardner(co
             // the window of the NEXT chunk is requested while this chunk's arithmetic runs (a chunk's 2 us of load latency
             // would otherwise be paid 512 times in a row: the producers, not the loop, set the pace above 4 samples per symbol)
             f32x4 pf[GW::loads];
-            uint32_t pf8[GW::loads];   // (FMT8) a pair of samples as it arrives
+            uint32_t pf8[GW::loads];   // (8-bit formats) a pair of samples as it arrives
             auto inside = [&](int cn) { return kGChunk * cn - GW::H >= 0 && kGChunk * cn - GW::H + GW::W <= n; };
             auto issue = [&](int cn) {
-                if (FMT8) {
+                if (wire_packed8(FMT)) {
                     // two 2-byte loads per pair from clamped positions, every chunk alike (masked where they are written)
 #pragma unroll
                     for (int k = 0; k < GW::loads; ++k) {
@@ -404,14 +398,14 @@ __global__ __launch_bounds__(NT > 0 ? 64 * kGWaves : 64) void k_tetra_gardner(co
                     for (int o = 0; o < 8; ++o) myring[((kGChunk * cn + 8 * gI) & (kGRing - 1)) + o] = make_float2(0.f, 0.f);
                 } else {
                     // window: HBM -> registers -> this wavefront's LDS rows (nobody else reads them: no barrier, only the wait)
-                    if (FMT8) {
+                    if (wire_packed8(FMT)) {
 #pragma unroll
                         for (int k = 0; k < GW::loads; ++k) {
                             const int ga = g0 + 2 * xpr[k];
                             if (k < GW::loads - 1 || lane + 64 * k < 8 * GW::pairs) {
                                 float2 *d = xw + xcar[k] * GW::pitch + GW::slot(2 * xpr[k]);
-                                d[0] = (ga >= 0 && ga < n) ? mf_convert8<FMT8 ? FMT8 : 1>(pf8[k]) : make_float2(0.f, 0.f);
-                                d[1] = (ga + 1 >= 0 && ga + 1 < n) ? mf_convert8<FMT8 ? FMT8 : 1>(pf8[k] >> 16) : make_float2(0.f, 0.f);
+                                d[0] = (ga >= 0 && ga < n) ? tetra_decode<wire_packed8(FMT) ? FMT : FMT_CU8>(pf8[k]) : make_float2(0.f, 0.f);
+                                d[1] = (ga + 1 >= 0 && ga + 1 < n) ? tetra_decode<wire_packed8(FMT) ? FMT : FMT_CU8>(pf8[k] >> 16) : make_float2(0.f, 0.f);
                             }
                         }
                     } else if (inside(cn)) {

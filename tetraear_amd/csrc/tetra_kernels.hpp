@@ -153,26 +153,27 @@ __device__ __forceinline__ void split_bf16(float a, float b, uint32_t &hi, uint3
     lo = pk_bf16(a - a1, b - b1);
 }
 
-// FMT8 (round 6; north_star: "coalesced complex-int8/float loads"): 0 = cf32 input; 1 = cu8, 2 = cs8 -- 2 bytes per sample
+// FMT (round 6; north_star: "coalesced complex-int8/float loads"): FMT_CF32 input; FMT_CU8, FMT_CS8 -- 2 bytes per sample
 // through HBM instead of 8 (algorithmic bytes per symbol at 4 samples/symbol: 17 instead of 41).  An 8-bit sample is EXACT in
 // one bf16 -- cu8 as the odd integer 2u - 255 (|.| <= 255: eight significant bits), cs8 as it is -- so the staged window has
 // ONE plane per component instead of a leading and a trailing one and the matched filter two matrix-core products per step
 // instead of four; the format's scale (1/255: x = u / 127.5 - 1 = (2u - 255) / 255; 1/128) multiplies the soft symbols where
 // they are stored -- everything between (timing statistic, estimates, interpolation) does not depend on the scale.
-template <int FMT8>
+// (This integer-plane form belongs to the kernel's bf16 planes; the format itself -- and the two scales -- is wire_format.hpp's.)
+template <int FMT>
 struct TetraIn8 {
-    static constexpr float scale = FMT8 == 1 ? 1.f / 255.f : (FMT8 == 2 ? 1.f / 128.f : 1.f);
+    static constexpr float scale = FMT == FMT_CU8 ? 0.5f * WireScale<FMT_CU8>::f32 : (FMT == FMT_CS8 ? WireScale<FMT_CS8>::f32 : 1.f);
     __device__ __forceinline__ static float2 conv(uint32_t h)   // low 16 bits: I, Q -> the integers the filter runs on
     {
-        if (FMT8 == 1) return make_float2(fmaf((float)(h & 255u), 2.f, -255.f), fmaf((float)((h >> 8) & 255u), 2.f, -255.f));   // (v_cvt_f32_ubyteN + one fma: exact)
+        if (FMT == FMT_CU8) return make_float2(fmaf((float)(h & 255u), 2.f, -255.f), fmaf((float)((h >> 8) & 255u), 2.f, -255.f));   // (v_cvt_f32_ubyteN + one fma: exact)
         return make_float2((float)(int8_t)(h & 255u), (float)(int8_t)((h >> 8) & 255u));
     }
 };
 
-// FMT8 == 3: cs16, int16 I then int16 Q, one 4-byte word per sample.  PACKED input like the 8-bit formats (converted where the
+// FMT_CS16: int16 I then int16 Q, one 4-byte word per sample.  PACKED input like the 8-bit formats (converted where the
 // window is staged: s * 2^-15, exact in fp32), but NOT one bf16 plane: a 16-bit integer needs the leading and the trailing bf16
 // (their sum is the sample exactly), so behind the staging it is the cf32 kernel -- four planes, four products, no scale at the store.
-template <int NT, int FMT8 = 0>
+template <int NT, int FMT = FMT_CF32>
 __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fused(const void *__restrict__ x_, int64_t in_stride,
                                                               const TetraParams P, float2 *__restrict__ soft,
                                                               uint8_t *__restrict__ hard, int32_t *n_soft,
@@ -182,8 +183,8 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     static_assert(kRrcPerThread == 8 && kRrcThreads % 64 == 0 && kTimingBlock == 256, "a wavefront owns two timing sub-blocks of a tile");
     static_assert(kRing % kTimingBlock == 0 && kRing - kRrcTile - kTimingBlock * (2 * kTimingHalfWin + 1) / 2 >= kTimingBlock / 2, "ring too short");
     constexpr int PER = kRrcPerThread;
-    constexpr bool K8 = FMT8 == 1 || FMT8 == 2;   // 8-bit input: one bf16 plane per component, the format's scale at the store
-    constexpr bool K16 = FMT8 == 3;               // cs16: packed input, cf32 arithmetic
+    constexpr bool K8 = wire_packed8(FMT);        // 8-bit input: one bf16 plane per component, the format's scale at the store
+    constexpr bool K16 = FMT == FMT_CS16;         // cs16: packed input, cf32 arithmetic
     constexpr int HALO = NT - 1, H2 = HALO / 2;
     constexpr int KS = (kRrcRun + HALO + 31) / 32;        // matrix-core steps (32 window positions each) per run of 16 outputs
     constexpr int NS = kRrcTile - kRrcRun + 32 * KS;      // samples staged per tile: base - H2 .. base - H2 + NS
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     const int n = P.n;
     const double sps = P.sps;
     const float2 *xr = (const float2 *)x_ + (int64_t)row * in_stride;     // rows of the channeliser may carry a pitch
-    const uint16_t *xr8 = (const uint16_t *)x_ + (int64_t)row * in_stride;   // (FMT8: one 2-byte sample per element)
+    const uint16_t *xr8 = (const uint16_t *)x_ + (int64_t)row * in_stride;   // (8-bit formats: one 2-byte sample per element)
     const uint32_t *xr16 = (const uint32_t *)x_ + (int64_t)row * in_stride;  // (cs16: one 4-byte sample per element)
     float2 *sr = soft + (int64_t)row * P.max_soft;
     const int nb = (n + kTimingBlock - 1) / kTimingBlock;
@@ -235,9 +236,9 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
     static_assert(NS / 2 - (NP - 1) * kRrcThreads <= 64, "the pairs of the last turn lie in wavefront 0");
     const bool last_turn = wv == 0;
     const int gmaxp = n - 2;                              // last pair start inside the chunk
-    const float2 x_first = FMT8 ? make_float2(0.f, 0.f) : xr[0], x_last = FMT8 ? make_float2(0.f, 0.f) : xr[n - 1];
+    const float2 x_first = wire_packed(FMT) ? make_float2(0.f, 0.f) : xr[0], x_last = wire_packed(FMT) ? make_float2(0.f, 0.f) : xr[n - 1];
     f32x4 pf[NP];
-    uint32_t pf8[NP];   // (FMT8) a pair of consecutive samples as it arrives: low half the first
+    uint32_t pf8[NP];   // (8-bit formats) a pair of consecutive samples as it arrives: low half the first
     typedef uint32_t u32pair __attribute__((ext_vector_type(2)));
     u32pair pf16[NP];   // (cs16) a pair of consecutive samples as it arrives
     auto fetch = [&](int tile) {
@@ -311,8 +312,8 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
             for (int j = 0; j < NP; ++j) {
                 if (j == NP - 1 && !last_turn) break;
                 const int idx = tid + j * kRrcThreads, g = g0 + 2 * idx;
-                const float2 e0 = (g >= 0 && g < n) ? tetra_conv16(pf16[j].x) : make_float2(0.f, 0.f);
-                const float2 e1 = (g + 1 >= 0 && g + 1 < n) ? tetra_conv16(pf16[j].y) : make_float2(0.f, 0.f);
+                const float2 e0 = (g >= 0 && g < n) ? tetra_decode<FMT_CS16>(pf16[j].x) : make_float2(0.f, 0.f);
+                const float2 e1 = (g + 1 >= 0 && g + 1 < n) ? tetra_decode<FMT_CS16>(pf16[j].y) : make_float2(0.f, 0.f);
                 put(idx, j == NP - 1, e0.x, e0.y, e1.x, e1.y);
             }
             return;
@@ -322,8 +323,8 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
             for (int j = 0; j < NP; ++j) {
                 if (j == NP - 1 && !last_turn) break;
                 const int idx = tid + j * kRrcThreads, g = g0 + 2 * idx;
-                const float2 e0 = (g >= 0 && g < n) ? TetraIn8<FMT8>::conv(pf8[j]) : make_float2(0.f, 0.f);
-                const float2 e1 = (g + 1 >= 0 && g + 1 < n) ? TetraIn8<FMT8>::conv(pf8[j] >> 16) : make_float2(0.f, 0.f);
+                const float2 e0 = (g >= 0 && g < n) ? TetraIn8<FMT>::conv(pf8[j]) : make_float2(0.f, 0.f);
+                const float2 e1 = (g + 1 >= 0 && g + 1 < n) ? TetraIn8<FMT>::conv(pf8[j] >> 16) : make_float2(0.f, 0.f);
                 if (j < NP - 1 || idx < NS / 2) {   // one plane per component: the integers are exact in bf16
                     xsb[idx] = pk_bf16(e0.x, e1.x);
                     xsb[2 * PLANE + idx] = pk_bf16(e0.y, e1.y);
@@ -696,7 +697,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
             for (int u = 0; u < SU; ++u)
                 if (kb + off + u * TSYM < k_end) {
                     float2 sv = farrow_eval(f[u]);
-                    if (K8) { sv.x *= TetraIn8<FMT8>::scale; sv.y *= TetraIn8<FMT8>::scale; }
+                    if (K8) { sv.x *= TetraIn8<FMT>::scale; sv.y *= TetraIn8<FMT>::scale; }
                     so[off + u * TSYM] = sv;
                     amax = fmaxf(amax, fmaxf(fabsf(sv.x), fabsf(sv.y)));
                 }
@@ -722,7 +723,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
                     for (int k2 = -3; k2 < NT; ++k2) {
                         const int idx = first + k2 + 3;
                         float2 q3 = make_float2(0.f, 0.f);
-                        if (idx >= 0 && idx < n) q3 = K8 ? TetraIn8<FMT8>::conv(xr8[idx]) : (K16 ? tetra_conv16(xr16[idx]) : xr[idx]);
+                        if (idx >= 0 && idx < n) q3 = K8 ? TetraIn8<FMT>::conv(xr8[idx]) : (K16 ? tetra_decode<FMT_CS16>(xr16[idx]) : xr[idx]);
                         if (k2 >= 0) {   // tap k2 multiplies x[first + k2 + e] for output e
                             const float h = P.taps[k2];
                             a0x = fmaf(h, q0.x, a0x); a0y = fmaf(h, q0.y, a0y);
@@ -739,7 +740,7 @@ __global__ __launch_bounds__(kRrcThreads, TDM_TETRA_WAVES(NT)) void k_tetra_fuse
                     f.y1 = make_float2(a2x, a2y);
                     f.y2 = make_float2(a3x, a3y);
                     float2 sv = farrow_eval(f);
-                    if (K8) { sv.x *= TetraIn8<FMT8>::scale; sv.y *= TetraIn8<FMT8>::scale; }
+                    if (K8) { sv.x *= TetraIn8<FMT>::scale; sv.y *= TetraIn8<FMT>::scale; }
                     sr[k - k_lo] = sv;
                     amax = fmaxf(amax, fmaxf(fabsf(sv.x), fabsf(sv.y)));
                 }

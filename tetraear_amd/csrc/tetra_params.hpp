@@ -5,14 +5,16 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "tetra_taps.hpp"
+#include "wire_format.hpp"
 
 namespace tdm {
 
 constexpr int kRrcMaxTaps = 96;
-// a cs16 sample (one word: int16 I in the low half, int16 Q in the high) as the value it means, s / 32768: exact in fp32
-__device__ __forceinline__ float2 tetra_conv16(uint32_t w)
+// a packed sample (cu8 / cs8 in the low 16 bits of w, cs16 the whole word) as the value it means (wire_format.hpp wire_f32)
+template <int FMT>
+__device__ __forceinline__ float2 tetra_decode(uint32_t w)
 {
-    return make_float2((float)(int16_t)(w & 65535u) * 0x1p-15f, (float)((int32_t)w >> 16) * 0x1p-15f);
+    return make_float2(wire_f32<FMT>(wire_code_i<FMT>(w)), wire_f32<FMT>(wire_code_q<FMT>(w)));
 }
 #define TDM_TETRA_THREADS 256
 constexpr int kRrcThreads = TDM_TETRA_THREADS;            // 256: three workgroups per CU fit in LDS (0.465 ms per 4096 x 32768); 512: two (0.48 ms)
@@ -52,21 +54,21 @@ struct TetraParams {
 // one launch of the fused receiver on `rows` carriers; returns false when no kernel is instantiated for tp.ntaps
 // row_list / n_rows (device, or null): the launch covers the rows listed -- workgroup i takes row row_list[i], workgroups
 // past *n_rows leave at once -- instead of all `rows`
-// fmt8: 0 cf32 input, 1 cu8, 2 cs8 (tetra_kernels.hpp TetraIn8), 3 cs16 (packed input, the cf32 arithmetic)
-bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *soft, uint8_t *hard,
+// fmt: FMT_CF32 input, FMT_CU8 / FMT_CS8 (tetra_kernels.hpp TetraIn8) or FMT_CS16 (packed input, the cf32 arithmetic)
+bool tetra_launch(const TetraParams &tp, int rows, const void *x, int fmt, int64_t in_stride, float2 *soft, uint8_t *hard,
                   int32_t *n_soft, int32_t *timing_milli, double *min_margin, hipStream_t stream, const int32_t *row_list = nullptr,
                   const int32_t *n_rows = nullptr);
 
 // TDM_MODE_TETRA_GARDNER (tetra_gardner_kernels.hpp): the three launches, each on its own so that the caller can time them.
 // y: [rows][y_pitch] cf32 matched-filter output (y_pitch even, >= tp.n); false when no kernel is instantiated for tp.ntaps
-// fmt8: 0 cf32 input, 1 cu8, 2 cs8, 3 cs16 (converted where the window is staged)
-bool tetra_mf_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *y, int64_t y_pitch, hipStream_t stream);
+// fmt: FMT_CF32 input, FMT_CU8, FMT_CS8 or FMT_CS16 (converted where the window is staged)
+bool tetra_mf_launch(const TetraParams &tp, int rows, const void *x, int fmt, int64_t in_stride, float2 *y, int64_t y_pitch, hipStream_t stream);
 void tetra_gardner_loop_launch(const TetraParams &tp, int rows, const float2 *y, int64_t y_pitch, float2 *soft, int32_t *n_soft,
                                int32_t *timing_milli, hipStream_t stream);
 // the matched filter and the loop in ONE kernel (the filter output stays in LDS); false when not instantiated for tp.ntaps
 // (the caller then makes the three launches)
 int tetra_gardner_fused_per_cu(int ntaps);                 // workgroups of the fused kernel a compute unit holds (0: not instantiated)
-bool tetra_gardner_fused_available(int ntaps, int rows, int fmt8 = 0);   // fmt8: tetra_launch's   // instantiated for the tap count, and not slower than the three launches at this size
+bool tetra_gardner_fused_available(int ntaps, int rows, int fmt = FMT_CF32);   // fmt: tetra_launch's   // instantiated for the tap count, and not slower than the three launches at this size
 // seg (tetra_gardner_kernels.hpp GardnerSeg, or null): the carriers as two virtual carriers each (tp.n = a half's length,
 // rows = 2 x the physical carriers, outputs into the caller's temporaries); tetra_decide_launch joins them afterwards
 // Two segments per carrier (rounds of 4096 carriers or fewer: one loop wavefront per compute unit leaves seven eighths of the
@@ -96,7 +98,7 @@ struct GardnerSeg {
     int32_t ff_first;
 };
 
-bool tetra_gardner_fused_launch(const TetraParams &tp, int rows, const void *x, int fmt8, int64_t in_stride, float2 *soft, int32_t *n_soft,
+bool tetra_gardner_fused_launch(const TetraParams &tp, int rows, const void *x, int fmt, int64_t in_stride, float2 *soft, int32_t *n_soft,
                                 int32_t *timing_milli, hipStream_t stream, const GardnerSeg *seg = nullptr);
 // seg != null: the carriers' pieces are joined first (k_tetra_gardner_join): soft_b [(pieces - 1) rows][cap_b] the symbols of
 // pieces 1.., n_v / timing_v [pieces rows] the pieces' counts and timing; soft / n_soft / timing_milli receive the joined carrier

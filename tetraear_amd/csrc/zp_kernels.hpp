@@ -14,31 +14,10 @@
 #pragma once
 #include <math.h>
 
+#include "wire_format.hpp"   // (with mul_rn / add_rn / sub_rn, the exact-rounding helpers the slicer products use too)
 #include "zp_common.hpp"
 
 namespace tdm {
-
-// ------------------------------------------------------------------------------------------
-// exact-rounding helpers (no FMA contraction) for the few places where the reference's own
-// rounding sequence defines the data (cu8 -> float conversion, slicer products)
-// ------------------------------------------------------------------------------------------
-// (HIP's __dmul_rn / __dsub_rn are plain operators and get contracted into one v_fma_f64 with a neighbouring
-// operation under the default -ffp-contract=fast-honor-pragmas; the pragma is what keeps the two roundings)
-TDM_HD double mul_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a * b;
-}
-TDM_HD double add_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
-TDM_HD double sub_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a - b;
-}
 
 #if defined(__HIPCC__)
 #define TDM_NOINLINE __host__ __device__ __attribute__((noinline))
@@ -195,30 +174,17 @@ typedef NcoRunT<kWave> NcoRun;   // a lane of the staged loader visits j, j + 64
 // ------------------------------------------------------------------------------------------
 // Loaders: give a lane its L consecutive samples of the padded, odd-extended signal.
 // ------------------------------------------------------------------------------------------
-enum { FMT_CU8 = 0, FMT_CS8 = 1, FMT_CF32 = 2, FMT_CF64 = 3, FMT_CS16 = 4 };
-
 template <int FMT>
 TDM_HD void convert_one(const void *rowp, int64_t k, double &re, double &im)
 {
-    if (FMT == FMT_CU8) {
-        // pyrtlsdr: iq = bytes.astype(float64).view(complex128); iq /= 127.5; iq -= (1+1j)
-        // numpy's complex/real division multiplies by fl(1/127.5): two roundings, no FMA.
-        const uint8_t *p = (const uint8_t *)rowp + 2 * k;
-        const double c = 1.0 / 127.5;
-        re = sub_rn(mul_rn((double)p[0], c), 1.0);
-        im = sub_rn(mul_rn((double)p[1], c), 1.0);
-    } else if (FMT == FMT_CS8) {
-        const int8_t *p = (const int8_t *)rowp + 2 * k;
-        re = (double)p[0] * (1.0 / 128.0);
-        im = (double)p[1] * (1.0 / 128.0);
+    if constexpr (wire_packed(FMT)) {
+        const typename WireScale<FMT>::code *p = (const typename WireScale<FMT>::code *)rowp + 2 * k;
+        re = wire_f64<FMT>(p[0]);
+        im = wire_f64<FMT>(p[1]);
     } else if (FMT == FMT_CF32) {
         const float *p = (const float *)rowp + 2 * k;
         re = (double)p[0];
         im = (double)p[1];
-    } else if (FMT == FMT_CS16) {
-        const int16_t *p = (const int16_t *)rowp + 2 * k;   // s / 32768, exact
-        re = (double)p[0] * 0x1p-15;
-        im = (double)p[1] * 0x1p-15;
     } else {
         const double *p = (const double *)rowp + 2 * k;
         re = p[0];
@@ -234,7 +200,7 @@ struct RawLoader {
     double fs;
     int32_t rows_per_chunk;    // > 1: that many consecutive plan rows read the same input row (RawLoaderRT::rows_per_chunk)
 
-    static constexpr int kBytes = (FMT == FMT_CU8 || FMT == FMT_CS8) ? 2 : (FMT == FMT_CS16 ? 4 : (FMT == FMT_CF32 ? 8 : 16));
+    static constexpr int kBytes = wire_bytes(FMT);
     static constexpr bool kStaged = false;  // lanes load their own segment straight from memory
 
     TDM_HD const void *row_ptr(int row) const
@@ -263,16 +229,8 @@ struct RawLoader {
                 for (int d = 0; d < 4; ++d)
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const uint32_t s = ww[d] >> (16 * h);
                         const int idx = c * 8 + d * 2 + h;
-                        if (FMT == FMT_CU8) {
-                            const double cc = 1.0 / 127.5;
-                            xr[idx] = sub_rn(mul_rn((double)(s & 255u), cc), 1.0);
-                            xi[idx] = sub_rn(mul_rn((double)((s >> 8) & 255u), cc), 1.0);
-                        } else {
-                            xr[idx] = (double)(int8_t)(s & 255u) * (1.0 / 128.0);
-                            xi[idx] = (double)(int8_t)((s >> 8) & 255u) * (1.0 / 128.0);
-                        }
+                        wire_f64<wire_packed8(FMT) ? FMT : FMT_CU8>(ww[d] >> (16 * h), xr[idx], xi[idx]);
                     }
             }
         } else if (FMT == FMT_CS16 && aligned && L % 4 == 0) {
@@ -282,10 +240,7 @@ struct RawLoader {
                 const u32x4 w = v[c];
                 const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    xr[c * 4 + d] = (double)(int16_t)(ww[d] & 65535u) * 0x1p-15;
-                    xi[c * 4 + d] = (double)((int32_t)ww[d] >> 16) * 0x1p-15;
-                }
+                for (int d = 0; d < 4; ++d) wire_f64<FMT_CS16>(ww[d], xr[c * 4 + d], xi[c * 4 + d]);
             }
         } else if (FMT == FMT_CF64 && aligned) {
             const f64x2 *v = (const f64x2 *)p;

@@ -5,13 +5,13 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import FMT_BYTES, check, ptr
 
-_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cf64": 3, "cs16": 4}
+ACCEPTS = _lib.wire_codes("cu8", "cs8", "cf32", "cf64", "cs16")
 FIELDS = ("peak_freq_offset", "signal_power", "peak_power", "noise_floor", "snr", "strong", "afc")
 
 
 def spectrum_gate(iq, fmt, n_samples, rows=1, sample_rate=2.4e6, device=0):
     """iq: `rows` streams of n_samples back to back.  Returns (list of dicts per row, afc array)."""
-    f = _FMT_OF[fmt]
+    f = ACCEPTS[fmt]
     iq = np.ascontiguousarray(iq)
     assert iq.nbytes >= rows * n_samples * FMT_BYTES[f]
     out = np.zeros((rows, 8))

@@ -26,7 +26,6 @@ import numpy as np
 from tetraear_amd import _lib
 from tetraear_amd._lib import check, ptr
 from tetraear_amd.batch import BatchDemodulator
-from tetraear_amd.channeliser import _FMT_OF as _CHAN_FMT
 from tetraear_amd.channeliser import StreamingChanneliser
 from tetraear_amd.stream import StreamingDemodulator
 
@@ -251,7 +250,7 @@ def iter_channels(source, M, D, chunk, fmt="cu8", streams=1, device=0):
     and yields that read's channel block, complex64 [streams][M][n_out] -- the last, shorter read as it is (its bytes split
     evenly between the streams).  The blocks go through one StreamingChanneliser, so concatenated along time they equal one
     channelise_batch call over the whole source; n_out varies from read to read (ceil / floor of chunk / D) and may be 0."""
-    fb = _lib.FMT_BYTES[_CHAN_FMT[fmt]]
+    fb = _lib.WIRE_FORMATS[fmt][1]
     streams, chunk = int(streams), int(chunk)
     readinto, close = _open(source)
     buf = np.empty(streams * chunk * fb, dtype=np.uint8)

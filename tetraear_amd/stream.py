@@ -22,9 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import FMT_BYTES, FMT_CF32, FMT_CF64, FMT_CS8, FMT_CU8, MODE_REFERENCE, check
 
-_FMT_OF = {"cu8": FMT_CU8, "cs8": FMT_CS8, "cf32": FMT_CF32, "cf64": FMT_CF64}
-# the numpy view of an input slot: cu8 / cs8 as interleaved bytes, cf32 / cf64 as complex samples
-_VIEW_DTYPE = {FMT_CU8: np.uint8, FMT_CS8: np.int8, FMT_CF32: np.complex64, FMT_CF64: np.complex128}
+ACCEPTS = _lib.wire_codes("cu8", "cs8", "cf32", "cf64")   # (tdm_stream_create does not take cs16)
 
 
 class StreamingDemodulator:
@@ -37,7 +35,7 @@ class StreamingDemodulator:
                  pre_shifts=None, rows_per_chunk=1, device=0):
         self.lib = _lib.load()
         self.handle = None
-        self.fmt = _FMT_OF[fmt] if isinstance(fmt, str) else int(fmt)
+        self.fmt = ACCEPTS[fmt] if isinstance(fmt, str) else int(fmt)
         self.chunk, self.rows, self.depth, self.device = int(chunk), int(rows), int(depth), device
         self.rows_per_chunk = int(rows_per_chunk)
         self.in_rows = self.rows // max(self.rows_per_chunk, 1)
@@ -70,7 +68,8 @@ class StreamingDemodulator:
         if self._acquired is None:
             p, seq = C.c_void_p(), C.c_int64()
             check(self.lib.tdm_stream_acquire(self.handle, C.byref(p), C.byref(seq)))
-            dt = np.dtype(_VIEW_DTYPE[self.fmt])
+            # the numpy view of an input slot: cu8 / cs8 as interleaved bytes, cf32 / cf64 as complex samples
+            dt = np.dtype(_lib.FMT_VIEW_DTYPE[self.fmt])
             count = self.in_rows * self.chunk * FMT_BYTES[self.fmt] // dt.itemsize
             view = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(count * dt.itemsize,)).view(dt)
             self._views.append(view)

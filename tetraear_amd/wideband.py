@@ -14,7 +14,7 @@ from ._lib import FMT_BYTES, MODE_TETRA, check
 from .batch import BatchDemodulator, DeviceBuffer
 from .channeliser import aligned_pitch
 
-_FMT_OF = {"cu8": 0, "cs8": 1, "cf32": 2, "cs16": 4}
+ACCEPTS = _lib.wire_codes("cu8", "cs8", "cf32", "cs16")
 
 
 class WidebandReceiver:
@@ -37,7 +37,7 @@ class WidebandReceiver:
         860 MB per 32-stream batch going out to HBM and coming back; sub-batches alternate between the slots, outputs of
         all sub-batches land in ONE set of output buffers (`out`)."""
         self.lib = _lib.load()
-        self.fmt = _FMT_OF[fmt]
+        self.fmt = ACCEPTS[fmt]
         self.device = device
         # gated: the reference demodulates only when its gate sees a signal (ui/modern.py:1921-2022).  For a channeliser's
         # rows: tdm_occupancy_gate decides on the device which rows are occupied and the receiver is launched over those
